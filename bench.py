@@ -12,12 +12,16 @@ shards over independent utterances, so there is no data-path collective; RCCL
 (torch.distributed "nccl") is used only for the barrier, the max-over-ranks
 timer and the frame count.  ``value`` = frames of all ranks / max rank time.
 
-Extra JSON fields: ``roofline`` for the dominant kernel (the persistent frame
-decoder at batch 1, else the decoder gate/up projection the batch runs), timed
-live with HIP events on the engine stream; ``roofline_backbone`` (backbone
-gate/up); ``roofline_frame`` (the weights a frame step reads x frame steps/s);
-and ``cpu_baseline`` (the numpy oracle, i.e. a CPU restatement -- NOT the MLX
-reference -- on this host).
+A plain run sets up, warms up, times the steps and prints the line;
+``--dump-outputs DIR`` also writes the last timed step's codes and PCM as .npy.
+Extra JSON field: ``roofline_frame`` (the weights a frame step reads x frame
+steps/s, from the timed steps themselves).
+
+``--full`` adds, after the timed steps: ``roofline`` for the dominant kernel (the
+persistent frame decoder at batch 1, else the decoder gate/up projection the
+batch runs), timed live with HIP events on the engine stream;
+``roofline_backbone`` (backbone gate/up); and ``cpu_baseline`` (the numpy
+oracle, i.e. a CPU restatement -- NOT the MLX reference -- on this host).
 """
 from __future__ import annotations
 
@@ -225,6 +229,33 @@ def model_codes(model, B):
     return [hist[: n[b], b] for b in range(B)]
 
 
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, codes, pcm, budget: int = DUMP_BYTES):
+    """--dump-outputs: what the last timed step handed its caller, as float32 ``out_dir/<name>.npy``:
+    ``frames`` (B,) frames per utterance, ``codes`` (sum of frames, K) the utterances' codes one after
+    the other (codes < 2^24: exact in float32) and, with the Mimi decode, ``pcm`` the utterances' samples
+    one after the other.  At most ``budget`` bytes in all: a longer PCM is cut down to a fixed sample
+    (seed 0, in order) whose positions go to ``pcm_index`` (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    K = codes[0].shape[1] if len(codes) else 0
+    arrs = {"frames": np.asarray([len(c) for c in codes], np.float32),
+            "codes": (np.concatenate(codes, 0) if len(codes) else np.zeros((0, K))).astype(np.float32)}
+    if arrs["codes"].nbytes + arrs["frames"].nbytes > budget:
+        raise SystemExit(f"bench.py: --dump-outputs: the codes alone exceed {budget} bytes")
+    if pcm is not None:
+        flat = np.concatenate([np.asarray(p, np.float32).ravel() for p in pcm]) if len(pcm) else np.zeros(0, np.float32)
+        room = budget - arrs["codes"].nbytes - arrs["frames"].nbytes
+        if flat.nbytes > room:
+            idx = np.unique(np.random.default_rng(0).integers(0, flat.size, room // 12))   # 4 B sample + 8 B index
+            arrs["pcm_index"] = idx.astype(np.float64)
+            flat = flat[idx]
+        arrs["pcm"] = flat
+    for name, a in arrs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def context_audio(g: int, seg: int, seconds: float = 5.0):
     """seeded sum of 3 sines (100-400 Hz) + N(0, 0.01) noise, amplitude 0.1, 24 kHz."""
     rng = np.random.default_rng(50_000 + 97 * g + seg)
@@ -390,6 +421,12 @@ def main():
     ap.add_argument("--model", default="csm_1b", choices=["csm_1b", "tiny"],
                     help="tiny: the toy test model (multi-rank rehearsals in tests), never a bench line")
     ap.add_argument("--dump", default="", help="rank 0 writes the gathered codes / PCM of the last step (npz)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned as DIR/<name>.npy (float32): codes, "
+                         "frames (per utterance) and, with the Mimi decode, pcm")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the live kernel "
+                         "rooflines (replays on the engine stream) and, on one GPU, the CPU baseline")
     ap.add_argument("--weights", default="bcast", choices=["bcast", "synthetic"],
                     help="N ranks: rank 0 builds the weights and broadcasts the engine buffers device to device "
                          "(bcast, default) or every rank generates them itself (synthetic)")
@@ -532,7 +569,7 @@ def main():
     total_frames, max_dt = aggregate(float(frames), dt, world, dev)
     dist_info = rank_report(float(frames), dt, args.steps, world, device, dev, gather_t[0])
 
-    roof = rooflines(model, args.batch, args.roofline_iters)
+    roof = rooflines(model, args.batch, args.roofline_iters) if args.full else None
     fb = frame_weight_bytes(model)
     frame_steps_per_s = total_frames / max_dt / max(1, args.batch * world)   # engine frame steps / s per GPU
     ach_f = fb * frame_steps_per_s / 1e9
@@ -554,6 +591,8 @@ def main():
         if last["pcm"] is not None:
             z.update({f"pcm_{i}": p for i, p in enumerate(last["pcm"])})
         np.savez(args.dump, n=len(last["codes"]), **z)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["codes"], last["pcm"])
     if rank == 0:
         line = {
             "metric": METRIC,
@@ -579,13 +618,14 @@ def main():
                        "weights": weights_info,
                        "results": results_info},
             "dist": dist_info,
-            "roofline": roof["dominant"],
-            "roofline_backbone": roof["backbone_gate_up"],
             "roofline_frame": roof_frame,
         }
+        if roof is not None:    # --full: the kernels' own replays, after the timed steps
+            line["roofline"] = roof["dominant"]
+            line["roofline_backbone"] = roof["backbone_gate_up"]
         if phases is not None:  # per-phase wall seconds of one step (synchronized boundaries: lab option)
             line["phases_s_per_step"] = {k: round(v / args.steps, 4) for k, v in phases.items()}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_frames)
         print(json.dumps(line), flush=True)
     if use_dist:

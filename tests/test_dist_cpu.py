@@ -139,6 +139,34 @@ def test_bench_world_size_mismatch_refused():
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: float32 .npy files of the step's codes / frames / PCM, exact; over the byte budget
+    the PCM becomes the same seeded in-order sample every time, with its positions beside it."""
+    import numpy as np
+    bench = _bench_mod()
+    rng = np.random.default_rng(3)
+    codes = [rng.integers(0, 2051, (f, 32)).astype(np.int32) for f in (5, 3)]
+    pcm = [rng.standard_normal(1920 * f).astype(np.float32) for f in (5, 3)]
+    bench.dump_outputs(str(tmp_path / "a"), codes, pcm)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("frames", "codes", "pcm")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["frames"].tolist() == [5, 3] and np.array_equal(got["codes"], np.concatenate(codes))
+    assert np.array_equal(got["pcm"], np.concatenate(pcm))
+    assert not (tmp_path / "a" / "pcm_index.npy").exists()
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), codes, pcm, budget=20_000)
+    files = sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert files == ["codes.npy", "frames.npy", "pcm.npy", "pcm_index.npy"]
+    assert sum((tmp_path / "b" / f).stat().st_size - 128 for f in files) <= 20_000
+    idx = np.load(tmp_path / "b" / "pcm_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "pcm.npy"), np.concatenate(pcm)[idx.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+    bench.dump_outputs(str(tmp_path / "d"), codes, None)
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["codes.npy", "frames.npy"]
+
+
 def _gather0_worker(rank, world, port, q):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

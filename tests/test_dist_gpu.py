@@ -35,11 +35,13 @@ def _free_port():
 
 
 def _bench(tmp_path, nproc, batch_per_rank, frames, name, backend="gloo", launcher=False, model="tiny",
-           dtype="float32", steps=1):
+           dtype="float32", steps=1, full=False):
     out = tmp_path / f"{name}.npz"
     args = [os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--model", model, "--dtype", dtype,
             "--batch", str(batch_per_rank), "--frames", str(frames), "--steps", str(steps), "--warmup", "0",
             "--dist-backend", backend, "--no-cpu-baseline", "--dump", str(out)]
+    if full:                                    # the live kernel rooflines
+        args.append("--full")
     if launcher:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), *args]
@@ -90,7 +92,7 @@ def test_rccl_world1_persistent_kernels(tmp_path):
     nccl group, two timed steps with the per-step gather to rank 0 between them: codes identical to the
     plain single-process run, and the line names what the communicator saw."""
     line_n, codes_n, _ = _bench(tmp_path, 1, 1, 24, "nccl_pk", backend="nccl", launcher=True, model="csm_1b",
-                                dtype="bf16", steps=2)
+                                dtype="bf16", steps=2, full=True)
     assert line_n["dist"]["backend"] == "nccl" and line_n["dist"]["world_size_seen"] == 1
     assert len(line_n["dist"]["ranks"]) == 1 and line_n["dist"]["ranks"][0]["frames"] == 2 * 24
     assert line_n["roofline"]["kernel"].startswith("dec_frame_kernel"), line_n["roofline"]["kernel"]
