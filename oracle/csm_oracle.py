@@ -24,6 +24,10 @@ sources line by line as a spec:
 Sampling with temperature cannot reproduce MLX's RNG; it restates the build's
 own counter-based Gumbel-max sampler (``gumbel_u``) so GPU sampled codes can be
 checked bit-for-bit against this file.
+
+``OracleCSM(..., dtype=np.float64)`` evaluates the same stored parameters in
+float64 (the truth the float32 evaluations, this one and the GPU's, are measured
+against); the default is the fp32 restatement.
 """
 from __future__ import annotations
 
@@ -33,6 +37,18 @@ from typing import Dict, List, Optional
 import numpy as np
 
 F32 = np.float32
+F64 = np.float64
+
+
+def _dt(x):
+    """The evaluation precision follows the activations: float64 in, float64 arithmetic and out; anything
+    else is the float32 restatement (the default, bit for bit what it always was)."""
+    return F64 if getattr(x, "dtype", None) == F64 else F32
+
+
+def _dense(w, dt):
+    """A stored matrix as an array: lazy int4 triples (quant_oracle.QuantMatrix) dequantize in ``dt``."""
+    return w.dense(dt) if hasattr(w, "dense") else w.astype(dt, copy=False)   # (explicit: a mixed matmul is slow)
 
 
 # ----------------------------------------------------------------------------- RoPE
@@ -64,28 +80,32 @@ def rope_cache(theta: np.ndarray, max_seq_len: int = 2048) -> np.ndarray:
 
 
 def rope_apply(x: np.ndarray, cache: np.ndarray, offset: int) -> np.ndarray:
-    """attention.py:119-177: interleaved pairs (2i, 2i+1), fp32.  x: (B, T, H, hd)."""
+    """attention.py:119-177: interleaved pairs (2i, 2i+1), fp32.  x: (B, T, H, hd).
+    A float64 x is rotated in float64 by the same float32 table (the table is input data)."""
+    dt = _dt(x)
     b, t, h, hd = x.shape
     if offset + t > cache.shape[0]:
         raise ValueError("RoPE position beyond the cached 2048-position table (attention.py:152)")
     c = cache[offset: offset + t].reshape(1, t, 1, hd // 2, 2)
-    xs = x.astype(F32).reshape(b, t, h, hd // 2, 2)
+    xs = x.astype(dt).reshape(b, t, h, hd // 2, 2)
     x0, x1 = xs[..., 0], xs[..., 1]
     out = np.stack([x0 * c[..., 0] - x1 * c[..., 1], x1 * c[..., 0] + x0 * c[..., 1]], axis=-1)
-    return out.reshape(b, t, h, hd).astype(F32)
+    return out.reshape(b, t, h, hd).astype(dt)
 
 
 # ----------------------------------------------------------------------------- blocks
 def rms_norm(x: np.ndarray, w: np.ndarray, eps: float) -> np.ndarray:
     """mlx fast.rms_norm: x * rsqrt(mean(x^2) + eps) * w, fp32 internally."""
-    x = x.astype(F32)
-    ms = np.mean(x * x, axis=-1, keepdims=True, dtype=F32)
-    return (x * (F32(1) / np.sqrt(ms + F32(eps))) * w).astype(F32)
+    dt = _dt(x)
+    x = x.astype(dt)
+    ms = np.mean(x * x, axis=-1, keepdims=True, dtype=dt)
+    return (x * (dt(1) / np.sqrt(ms + dt(eps))) * w).astype(dt)
 
 
 def linear(x: np.ndarray, w: np.ndarray) -> np.ndarray:
     """nn.Linear without bias: y = x @ W.T with W (out, in)."""
-    return np.matmul(x, w.T).astype(F32)
+    dt = _dt(x)
+    return np.matmul(x, _dense(w, dt).T).astype(dt)
 
 
 def adapted_linear(x: np.ndarray, w: np.ndarray, ad: Optional[dict]) -> np.ndarray:
@@ -95,41 +115,44 @@ def adapted_linear(x: np.ndarray, w: np.ndarray, ad: Optional[dict]) -> np.ndarr
     y = linear(x, w)
     if ad is None:
         return y
-    z = (y + F32(ad["scale"]) * np.matmul(np.matmul(x, ad["a"]), ad["b"])).astype(F32)
+    dt = _dt(x)
+    z = (y + dt(ad["scale"]) * np.matmul(np.matmul(x, ad["a"]), ad["b"])).astype(dt)
     if ad.get("m") is not None:
-        wf = w + (F32(ad["scale"]) * ad["b"].T) @ ad["a"].T
-        z = (ad["m"] / np.linalg.norm(wf, axis=1).astype(F32)).astype(F32) * z
-    return z.astype(F32)
+        wf = _dense(w, dt) + (dt(ad["scale"]) * ad["b"].T) @ ad["a"].T
+        z = (ad["m"] / np.linalg.norm(wf, axis=1).astype(dt)).astype(dt) * z
+    return z.astype(dt)
 
 
-def adapted_embedding(idx: np.ndarray, w: np.ndarray, ad: Optional[dict]) -> np.ndarray:
+def adapted_embedding(idx: np.ndarray, w: np.ndarray, ad: Optional[dict], dt=F32) -> np.ndarray:
     """mlx_lm LoRAEmbedding / DoRAEmbedding forward: y = E[i] + scale A[i] B, DoRA rows rescaled
-    by m[i] / ||E[i] + scale A[i] B||."""
-    y = w[idx]
+    by m[i] / ||E[i] + scale A[i] B||.  ``dt``: the evaluation precision (the rows convert exactly)."""
+    y = w.rows(idx, dt) if hasattr(w, "rows") else w[idx].astype(dt, copy=False)
     if ad is None:
         return y
-    z = (y + np.matmul(ad["a"][idx], F32(ad["scale"]) * ad["b"])).astype(F32)
+    z = (y + np.matmul(ad["a"][idx], dt(ad["scale"]) * ad["b"])).astype(dt)
     if ad.get("m") is not None:
-        z = (ad["m"][idx] / np.linalg.norm(z, axis=-1).astype(F32))[..., None] * z
-    return z.astype(F32)
+        z = (ad["m"][idx] / np.linalg.norm(z, axis=-1).astype(dt))[..., None] * z
+    return z.astype(dt)
 
 
 def silu(x):
-    return (x / (F32(1) + np.exp(-x))).astype(F32)
+    dt = _dt(x)
+    return (x / (dt(1) + np.exp(-x))).astype(dt)
 
 
 def sdpa(q, k, v, scale, causal_offset: Optional[int]):
     """softmax(q k^T * scale + mask) v; q (B,H,T,hd), k/v (B,H,S,hd); causal iff T>1."""
-    s = np.matmul(q, np.swapaxes(k, -1, -2)).astype(F32) * F32(scale)
+    dt = _dt(q)
+    s = np.matmul(q, np.swapaxes(k, -1, -2)).astype(dt) * dt(scale)
     T, S = q.shape[2], k.shape[2]
     if causal_offset is not None and T > 1:
         qi = np.arange(T)[:, None] + causal_offset
         kj = np.arange(S)[None, :]
-        s = np.where(kj <= qi, s, F32(-np.inf))
+        s = np.where(kj <= qi, s, dt(-np.inf))
     s = s - s.max(-1, keepdims=True)
     p = np.exp(s)
     p = p / p.sum(-1, keepdims=True)
-    return np.matmul(p.astype(F32), v).astype(F32)
+    return np.matmul(p.astype(dt), v).astype(dt)
 
 
 class KVCacheRef:
@@ -150,9 +173,14 @@ class KVCacheRef:
 class LlamaRef:
     """mlx_lm LlamaModel with embed_tokens=Identity and the reference Attention patched in."""
 
-    def __init__(self, w: Dict[str, np.ndarray], prefix: str, args, adapters: Optional[Dict[str, dict]] = None):
+    def __init__(self, w: Dict[str, np.ndarray], prefix: str, args, adapters: Optional[Dict[str, dict]] = None,
+                 dtype=F32, mat=None):
+        """dtype: the evaluation precision (float32, or float64 on the same stored parameters);
+        mat: name -> the matrix handed to ``linear`` (OracleCSM.mat; default: the stored one)."""
         self.w, self.p, self.a = w, prefix, args
         self.adapters = adapters or {}
+        self.dt = dtype
+        self.mat = mat or w.__getitem__
         rs = args.rope_scaling
         theta = llama3_rope_theta(args.head_dim, args.rope_theta, rs.get("factor", 1.0),
                                   1.0, 4.0, 8192)   # attention.py:201-205 passes only base/scale_factor
@@ -178,19 +206,20 @@ class LlamaRef:
         return self.lin(o, f"{p}.o_proj")
 
     def lin(self, x, path):
-        return adapted_linear(x, self.w[path + ".weight"], self.adapters.get(path))
+        return adapted_linear(x, self.mat(path + ".weight"), self.adapters.get(path))
 
     def __call__(self, x, caches: List[KVCacheRef]):
         a, w = self.a, self.w
-        h = x.astype(F32)
+        dt = self.dt
+        h = x.astype(dt)
         for i in range(a.num_hidden_layers):
             p = f"{self.p}.layers.{i}"
             r = self.attention(i, rms_norm(h, w[f"{p}.input_layernorm.weight"], a.rms_norm_eps), caches[i])
-            h = (h + r).astype(F32)
+            h = (h + r).astype(dt)
             n = rms_norm(h, w[f"{p}.post_attention_layernorm.weight"], a.rms_norm_eps)
             g = self.lin(n, f"{p}.mlp.gate_proj")
             u = self.lin(n, f"{p}.mlp.up_proj")
-            h = (h + self.lin((silu(g) * u).astype(F32), f"{p}.mlp.down_proj")).astype(F32)
+            h = (h + self.lin((silu(g) * u).astype(dt), f"{p}.mlp.down_proj")).astype(dt)
         return rms_norm(h, w[f"{self.p}.norm.weight"], a.rms_norm_eps)
 
 
@@ -274,9 +303,9 @@ def sample_one(logits: np.ndarray, temperature: float, top_k: int, seed: int, st
                top_p: float = 0.0, min_p: float = 0.0, min_keep: int = 1) -> int:
     """Greedy = first max (mx.argmax); else Gumbel-max of logits*(1/temp) over the kept set
     (top-k; with top_p / min_p the mlx_lm filter chain, ``filter_keep``)."""
-    logits = logits.astype(F32)
     if temperature == 0:
-        return int(np.argmax(logits))
+        return int(np.argmax(logits.astype(_dt(logits))))
+    logits = logits.astype(F32)
     keep = filter_keep(logits, top_k, top_p, min_p, min_keep)
     scaled = (logits * (F32(1.0) / F32(temperature))).astype(F32).astype(np.float64)
     u = gumbel_u(seed, step, logits.shape[-1])
@@ -290,42 +319,72 @@ class OracleCSM:
     """Restatement of ``CSM`` (models.py:31-92) + ``generate_frame`` (generation.py:21-92)."""
 
     def __init__(self, args, weights: Dict[str, np.ndarray], bb_args, dec_args,
-                 adapters: Optional[Dict[str, dict]] = None):
-        """adapters: module path -> LoRA/DoRA tensors (see ``adapted_linear``), applied unfused."""
+                 adapters: Optional[Dict[str, dict]] = None, dtype=np.float32):
+        """adapters: module path -> LoRA/DoRA tensors (see ``adapted_linear``), applied unfused.
+        dtype: np.float32 (the restatement) or np.float64: every operation (embedding sums, RMSNorm,
+        matmuls, RoPE application, SDPA, SiLU, heads) in float64 on the SAME stored parameters, converted
+        exactly where they are used -- the truth the float32 paths (this oracle's and the GPU's) are
+        measured against.  The RoPE table stays the float32 table the engine is given (input data).
+        A weight may be a ``quant_oracle.QuantMatrix`` (packed, scales, biases): it dequantizes in the
+        evaluation precision, so the float64 reference of an int4 model is exact ``scale*q + bias``."""
+        if dtype not in (np.float32, np.float64):
+            raise ValueError("dtype must be np.float32 or np.float64")
         self.args = args
-        self.w = {k: np.asarray(v, dtype=F32) for k, v in weights.items()}
+        self.dt = dtype
+        self.w = {k: v if hasattr(v, "dense") else np.asarray(v, dtype=F32) for k, v in weights.items()}
         self.ad = adapters or {}
-        self.backbone = LlamaRef(self.w, "backbone", bb_args, self.ad)
-        self.decoder = LlamaRef(self.w, "decoder", dec_args, self.ad)
+        self._up = {}
+        self.backbone = LlamaRef(self.w, "backbone", bb_args, self.ad, dtype, self.mat)
+        self.decoder = LlamaRef(self.w, "decoder", dec_args, self.ad, dtype, self.mat)
         self.bb_args, self.dec_args = bb_args, dec_args
         self.V, self.K = args.n_audio_vocab, args.n_audio_codebooks
         self.debug = {}
+
+    def mat(self, name: str):
+        """The matrix ``linear`` multiplies by.  float32: the stored array.  float64: the stored array too
+        (``linear`` converts it exactly for the product, a temporary), except the depth decoder's and the
+        projection's, which every codebook step reuses: those are kept converted (~0.9 GB for csm_1b)
+        until ``drop_upcasts``.  No float64 copy of the whole model is ever held."""
+        w = self.w[name]
+        if self.dt is F32 or not (name.startswith("decoder.") or name == "projection.weight"):
+            return w
+        if name not in self._up:
+            self._up[name] = np.ascontiguousarray(_dense(w, F64), dtype=F64)
+        return self._up[name]
+
+    def drop_upcasts(self):
+        self._up.clear()
 
     def new_backbone_cache(self):
         return [KVCacheRef() for _ in range(self.bb_args.num_hidden_layers)]
 
     def embed_audio(self, codebook: int, tokens: np.ndarray) -> np.ndarray:
         return adapted_embedding(tokens + codebook * self.V, self.w["audio_embeddings.weight"],
-                                 self.ad.get("audio_embeddings"))                    # models.py:79-80
+                                 self.ad.get("audio_embeddings"), self.dt)           # models.py:79-80
 
     def embed_tokens(self, tokens: np.ndarray) -> np.ndarray:                   # models.py:82-92
         text = adapted_embedding(tokens[:, :, -1], self.w["text_embeddings.weight"],
-                                 self.ad.get("text_embeddings"))[:, :, None, :]
+                                 self.ad.get("text_embeddings"), self.dt)[:, :, None, :]
         audio_tokens = tokens[:, :, :-1] + self.V * np.arange(self.K)
         audio = adapted_embedding(audio_tokens.reshape(-1), self.w["audio_embeddings.weight"],
-                                  self.ad.get("audio_embeddings")).reshape(*tokens.shape[:2], self.K, -1)
+                                  self.ad.get("audio_embeddings"), self.dt).reshape(*tokens.shape[:2], self.K, -1)
         return np.concatenate([audio, text], axis=-2)
 
     def frame(self, tokens, mask, cache, temperature=0.0, top_k=0, seeds=None, frame_idx=0,
-              processors=None, c0_history=None, top_p=0.0, min_p=0.0, min_keep=1, sampler=None):
+              processors=None, c0_history=None, top_p=0.0, min_p=0.0, min_keep=1, sampler=None, forced=None):
         """generation.py:21-92.  tokens/mask (B,T,33).  Returns codes (B,K) int32.
         processors: logits processors on c0 (:44-49), called with (stack(c0_history) or zeros((0,)),
         logits); c0 (B,1) is appended to c0_history when it is a list (:60-61).
         sampler: a callable logits (B, V) -> codes (B,) used for every codebook instead of the built-in
-        greedy / Gumbel sampler (the sampler= keyword of the reference CLI, cli/generate.py:197-199)."""
+        greedy / Gumbel sampler (the sampler= keyword of the reference CLI, cli/generate.py:197-199).
+        forced: codes (B, K) fed forward at every codebook instead of the sampled ones (teacher forcing:
+        the logits are computed as always; the frame returns ``forced``)."""
         B = tokens.shape[0]
-        emb = self.embed_tokens(tokens) * mask[..., None].astype(F32)              # :34-35
-        x = np.zeros(emb.shape[:2] + emb.shape[3:], F32)
+        dt = self.dt
+        if forced is not None:
+            forced = np.asarray(forced, np.int64).reshape(B, self.K)
+        emb = self.embed_tokens(tokens) * mask[..., None].astype(dt)               # :34-35
+        x = np.zeros(emb.shape[:2] + emb.shape[3:], dt)
         for j in range(emb.shape[2]):                                              # :36 sum over 33, in order
             x = x + emb[:, :, j]
         h = self.backbone(x, cache)                                                # :39
@@ -333,12 +392,14 @@ class OracleCSM:
         c0_logits = adapted_linear(h_last, self.w["codebook0_head.weight"], self.ad.get("codebook0_head"))  # :42
         for proc in processors or []:                                              # :44-49
             hist = np.stack(c0_history, 0) if c0_history else np.zeros((0,), np.int32)
-            c0_logits = np.asarray(proc(hist, c0_logits), F32)
+            c0_logits = np.asarray(proc(hist, c0_logits), dt)
         self.debug["c0_logits"] = c0_logits
         self.debug["h_last"] = h_last
         seeds = seeds if seeds is not None else [0] * B
         flt = dict(top_p=top_p, min_p=min_p, min_keep=min_keep)
-        if sampler is not None:
+        if forced is not None:
+            c0 = forced[:, 0]
+        elif sampler is not None:
             c0 = np.asarray(sampler(c0_logits), np.int64).reshape(B)
         else:
             c0 = np.array([sample_one(c0_logits[b], temperature, top_k, seeds[b], frame_idx * self.K, **flt)
@@ -353,9 +414,12 @@ class OracleCSM:
         for i in range(1, self.K):                                                 # :72
             z = self.decoder(adapted_linear(dec_in, self.w["projection.weight"], self.ad.get("projection")),
                              dcache)                                               # :74-77
-            logits = np.matmul(z[:, -1, :], self.w["audio_head"][i - 1]).astype(F32)   # :79 (in,out) layout
+            head = self.w["audio_head"][i - 1].astype(dt, copy=False)
+            logits = np.matmul(z[:, -1, :], head).astype(dt)                       # :79 (in,out) layout
             ci_logits_all.append(logits)
-            if sampler is not None:
+            if forced is not None:
+                ci = forced[:, i]
+            elif sampler is not None:
                 ci = np.asarray(sampler(logits), np.int64).reshape(B)
             else:
                 ci = np.array([sample_one(logits[b], temperature, top_k, seeds[b], frame_idx * self.K + i, **flt)

@@ -85,13 +85,38 @@ def unpack(packed: np.ndarray) -> np.ndarray:
     return q.reshape(N, W * 8)
 
 
-def dequantize(packed: np.ndarray, scales: np.ndarray, biases: np.ndarray, group_size: int = 64) -> np.ndarray:
-    """mx.dequantize: scale * q + bias per group (fp32)."""
-    q = unpack(packed).astype(F32)
-    N, K = q.shape
-    s = np.repeat(scales.astype(F32), group_size, axis=1)
-    b = np.repeat(biases.astype(F32), group_size, axis=1)
-    return (s * q + b).astype(F32)
+def dequantize(packed: np.ndarray, scales: np.ndarray, biases: np.ndarray, group_size: int = 64,
+               dtype=F32) -> np.ndarray:
+    """mx.dequantize: scale * q + bias per group, in ``dtype`` (fp32 as MLX does; float64 evaluates the
+    same stored triple without the fp32 rounding of the product and sum)."""
+    by = np.ascontiguousarray(packed, dtype="<u4").view(np.uint8)         # byte j: elements 2j (low), 2j+1
+    N, K = by.shape[0], by.shape[1] * 2
+    out = np.empty((N, K // 2, 2), dtype)
+    out[:, :, 0] = by & np.uint8(15)
+    out[:, :, 1] = by >> np.uint8(4)
+    out = out.reshape(N, K // group_size, group_size)
+    out *= scales.astype(dtype)[:, :, None]                               # one rounding per operation in
+    out += biases.astype(dtype)[:, :, None]                               # ``dtype``, as s * q + b
+    return out.reshape(N, K)
+
+
+class QuantMatrix:
+    """A quantized (N, K) parameter kept as its stored triple (packed, scales, biases): what a float64
+    evaluation starts from (``scale * q + bias`` is the exact definition of the weight; the fp32
+    ``dequantize`` result is already rounded).  ``dense`` / ``rows`` dequantize all / some rows."""
+
+    def __init__(self, packed, scales, biases, group_size: int = 64):
+        self.packed, self.scales, self.biases, self.group_size = packed, scales, biases, group_size
+        self.shape = (packed.shape[0], packed.shape[1] * 8)
+
+    def dense(self, dtype=F32) -> np.ndarray:
+        return dequantize(self.packed, self.scales, self.biases, self.group_size, dtype)
+
+    def rows(self, idx, dtype=F32) -> np.ndarray:
+        idx = np.asarray(idx)
+        flat = idx.reshape(-1)
+        out = dequantize(self.packed[flat], self.scales[flat], self.biases[flat], self.group_size, dtype)
+        return out.reshape(*idx.shape, self.shape[1])
 
 
 def quantized_names(names):
@@ -105,10 +130,16 @@ def quantized_names(names):
     return out
 
 
-def quantize_dequantize_weights(weights: dict, group_size: int = 64) -> dict:
-    """The fp32 weights an nn.quantize'd CSM computes with: w_hat for every quantized parameter."""
+def quantize_weights(weights: dict, group_size: int = 64) -> dict:
+    """name -> QuantMatrix for every parameter nn.quantize replaces (the stored form of the model)."""
+    return {n: QuantMatrix(*affine_quantize(np.asarray(weights[n], F32), group_size), group_size)
+            for n in quantized_names(list(weights))}
+
+
+def quantize_dequantize_weights(weights: dict, group_size: int = 64, quant: dict = None) -> dict:
+    """The fp32 weights an nn.quantize'd CSM computes with: w_hat for every quantized parameter.
+    quant: the result of ``quantize_weights(weights)`` when the caller already holds it."""
     out = dict(weights)
-    for n in quantized_names(list(weights)):
-        p, s, b = affine_quantize(np.asarray(weights[n], F32), group_size)
-        out[n] = dequantize(p, s, b, group_size)
+    for n, qm in (quant if quant is not None else quantize_weights(weights, group_size)).items():
+        out[n] = qm.dense(F32)
     return out

@@ -18,25 +18,72 @@ def csm_weights(args_key, seed=0):
 _ORACLES = {}
 
 
-def oracle_for(args, weights, bf16=False, q4=False):
+def oracle_for(args, weights, bf16=False, q4=False, f64=False):
     """bf16: every weight rounded to bf16 (CSM dtype "bf16").  q4: nn.quantize'd CSM (dtype "q4"):
     Linear / Embedding weights quantize->dequantize (oracle/quant_oracle.py), audio_head bf16.
+    f64: the float64 evaluation (OracleCSM dtype=np.float64) of the same stored parameters: it shares the
+    float32 oracle's arrays (bf16 / fp32) or starts from the int4 triples (q4), never a float64 model.
     Memoised per weight dict (the csm_weights dicts are cached): the csm_1b bf16 / int4 conversions
     take 10-45 s each (6 GB of fp32 per variant)."""
-    key = (id(weights), bool(bf16), bool(q4))
+    key = (id(weights), bool(bf16), bool(q4), bool(f64))
     if key not in _ORACLES:
-        _ORACLES[key] = _oracle_for(args, weights, bf16, q4)
+        _ORACLES[key] = _oracle_for(args, weights, bf16, q4, f64)
     return _ORACLES[key]
 
 
-def _oracle_for(args, weights, bf16, q4):
+_QUANT = {}
+
+
+def _quant_for(weights):
+    from oracle.quant_oracle import quantize_weights
+    if id(weights) not in _QUANT:
+        _QUANT[id(weights)] = quantize_weights(weights)
+    return _QUANT[id(weights)]
+
+
+def _oracle_for(args, weights, bf16, q4, f64=False):
     from oracle.csm_oracle import OracleCSM
     from oracle.quant_oracle import quantize_dequantize_weights
+    cfg = (BB[args.backbone_name], DC[args.decoder_name])
+    if f64:
+        w = dict(oracle_for(args, weights, bf16, q4).w)              # the float32 oracle's own arrays
+        if q4:
+            w.update(_quant_for(weights))                            # (packed, scales, biases): exact in float64
+        return OracleCSM(args, w, *cfg, dtype=np.float64)
     w = {k: bf16_round(v) for k, v in weights.items()} if bf16 else weights
     if q4:
-        w = quantize_dequantize_weights(weights)
+        w = quantize_dequantize_weights(weights, quant=_quant_for(weights))
         w["audio_head"] = bf16_round(weights["audio_head"])
-    return OracleCSM(args, w, BB[args.backbone_name], DC[args.decoder_name])
+    return OracleCSM(args, w, *cfg)
+
+
+def oracle_taps(o, prompts, codes):
+    """Teacher-forced taps of oracle ``o`` (either precision): prompts (tokens, mask) of any lengths, codes
+    (F, B, K) forced per frame.  Returns h_last (F, B, D), c0_logits (F, B, V), ci_logits (F, B, K-1, V)
+    in the oracle's precision.  Utterances of equal prompt length run as one batch."""
+    codes = np.asarray(codes)
+    F, B, K = codes.shape
+    assert B == len(prompts)
+    groups = {}
+    for i, (t, _) in enumerate(prompts):
+        groups.setdefault(t.shape[0], []).append(i)
+    out = None
+    for idx in groups.values():
+        toks = np.stack([prompts[i][0] for i in idx]).astype(np.int64)
+        msk = np.stack([prompts[i][1] for i in idx]).astype(bool)
+        cache = o.new_backbone_cache()
+        for f in range(F):
+            s = o.frame(toks, msk, cache, forced=codes[f, idx])
+            taps = [o.debug["h_last"], o.debug["c0_logits"], o.debug["ci_logits"]]
+            if out is None:
+                out = [np.zeros((F, B) + t.shape[1:], t.dtype) for t in taps]
+            for dst, t in zip(out, taps):
+                dst[f, idx] = t
+            toks = np.concatenate([s, np.zeros((len(idx), 1), np.int32)], 1)[:, None, :].astype(np.int64)
+            msk = np.concatenate([np.ones_like(s, bool), np.zeros((len(idx), 1), bool)], 1)[:, None, :]
+    if hasattr(o, "drop_upcasts"):
+        o.drop_upcasts()
+    return tuple(out)
 
 
 def prompt_ids(seed: int, n_mid: int = 12, vocab: int = 128000, bos: int = 128000, eos: int = 128001):
@@ -171,3 +218,69 @@ def eos_rig(args, w, alpha=EOS_RIG["alpha"], emb_norm=EOS_RIG["emb_norm"], head_
 def eos_weights(args_key="1b", seed=0):
     args, w = csm_weights(args_key, seed)
     return args, eos_rig(args, w)
+
+
+# ----------------------------------------------------------------------------- float64 taps: errors and the bar
+TAPS = ("h_last", "c0", "ci")
+# bar = BAR_MARGIN x e32.  Two float32 evaluations of the same arithmetic with different blocking and exp / rsqrt
+# implementations differ from the truth by the same order, so a healthy engine sits near 1 x e32 (measured on
+# the MI355X: 0.3-1.1 x over every path).  The margin is capped from above by what the
+# bar has to catch (tests/test_f64_oracle_cpu.py): 2 x bar must stay under the error of an evaluation that
+# loses the low activation bits of ONE projection kind of one stack, on the row / step that shows it least --
+# that error is 4.8 x e32 at its smallest (tiny, bf16 weights, the backbone's down_proj seen from ci), so a
+# margin of 4 would be over the cap; 2 holds it with room on both sides.
+BAR_MARGIN = 2.0
+
+
+def tap_errors(got, ref64):
+    """got / ref64: (h_last, c0_logits, ci_logits) as ``oracle_taps`` returns them.  Per tap the array of
+    max |got - float64| over the vocabulary (over D for h_last) / that row's largest |float64 value|:
+    one figure per frame and row (and codebook step for ci)."""
+    out = {}
+    for tap, g, r in zip(TAPS, got, ref64):
+        r = np.asarray(r, np.float64)
+        out[tap] = np.abs(np.asarray(g, np.float64) - r).max(-1) / np.abs(r).max(-1)
+    return out
+
+
+def f64_reference(args, weights, variant, prompts, codes):
+    """(float64 taps, e32) of a case: both oracles forced on ``codes`` (F, B, K); e32[tap] = the float32
+    oracle's largest error over rows, steps and frames -- measured from the references alone."""
+    kw = dict(bf16=variant == "bf16", q4=variant == "q4")
+    t64 = oracle_taps(oracle_for(args, weights, f64=True, **kw), prompts, codes)
+    t32 = oracle_taps(oracle_for(args, weights, **kw), prompts, codes)
+    return t64, {tap: float(e.max()) for tap, e in tap_errors(t32, t64).items()}
+
+
+# ----------------------------------------------------------------------------- one projection against float64
+def cut16(a):
+    """hi + mid of the matrix-core paths' activation split (csrc/xs.h split3): two truncations to bf16, the
+    second on the remainder -- what a path that loses the lo part computes with (16 significant bits)."""
+    a = np.ascontiguousarray(a, np.float32)
+    hi = (a.view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
+    r = (a - hi).astype(np.float32)
+    mid = (r.view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
+    return (hi + mid).astype(np.float32)
+
+
+def linear_f64_bar(x, w, n_cols=64, seed=0):
+    """For y = x @ w.T (x (M, K), w (N, K) float32): (y64, S, bar, defect) with y64 the float64 product,
+    S = sum |x||w| per output (the unit every error is divided by), bar = 1.5 x the largest error of a
+    left-to-right float32 accumulation of the float32 products -- the least favourable plain order --
+    over ``n_cols`` sampled output columns and every row, and defect = the largest error of the exact
+    product with x cut to 16 significant bits (``cut16``).  All from numpy, nothing from the engine."""
+    x64, w64 = x.astype(np.float64), w.astype(np.float64)
+    y64 = x64 @ w64.T
+    S = np.abs(x64) @ np.abs(w64).T
+    cols = np.sort(np.random.default_rng(seed).choice(w.shape[0], min(n_cols, w.shape[0]), replace=False))
+    prods = x[:, None, :] * w[None, cols, :]                                    # (M, cols, K) float32 products
+    lr = np.cumsum(prods, axis=-1, dtype=np.float32)[..., -1]                   # summed k = 0, 1, 2, ... in float32
+    bar = 1.5 * float(linear_err(lr, y64[:, cols], S[:, cols]))
+    defect = float(linear_err(cut16(x).astype(np.float64) @ w64.T, y64, S))
+    return y64, S, bar, defect
+
+
+def linear_err(y, y64, S):
+    """Largest |y - y64| / S; an output whose S is 0 (an all-zero weight row: padding) must be exactly 0."""
+    d = np.abs(np.asarray(y, np.float64) - y64)
+    return np.where(S > 0, d / np.where(S > 0, S, 1.0), np.where(d > 0, np.inf, 0.0)).max()
