@@ -37,12 +37,19 @@ def _headers_mtime():
     return max(os.path.getmtime(h) for h in hs if os.path.exists(h))
 
 
+def compile_cmd(src, obj, extra=(), name=None):
+    """The hipcc command that compiles one source the way the product build does: the base flags, the
+    per-source flags of ``name`` (default: src's own file name) and, for a lab variant, ``extra``."""
+    name = name or os.path.basename(src)
+    lang = ["-x", "hip"] if name.endswith(".hip") else []
+    return [HIPCC, *FLAGS, *SRC_FLAGS.get(name, []), *extra, *lang, "-c", src, "-o", obj]
+
+
 def _compile(src, hdr_mtime, verbose):
     obj = os.path.join(BUILD, os.path.basename(src) + ".o")
     if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_mtime):
         return obj
-    lang = ["-x", "hip"] if src.endswith(".hip") else []
-    cmd = [HIPCC, *FLAGS, *SRC_FLAGS.get(os.path.basename(src), []), *lang, "-c", src, "-o", obj]
+    cmd = compile_cmd(src, obj)
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     r = subprocess.run(cmd, capture_output=True, text=True)
@@ -67,5 +74,21 @@ def build(verbose: bool = False, jobs: int = 8) -> str:
     return LIB
 
 
-if __name__ == "__main__":
+def _main(argv):
+    # ``_build.py``: the product build.  ``_build.py compile <source name> <object> [flags...]``: one
+    # source (CSM_VARIANT_FILE=<path>: that file in its place) with the product's flags plus the given
+    # ones -- what tools/variant.sh and tools/fullvariant.sh build their A/B libraries from.
+    if argv[:1] == ["compile"]:
+        name, obj, extra = argv[1], argv[2], argv[3:]
+        src = os.path.join(CSRC, name)
+        if os.environ.get("CSM_VARIANT_FILE"):  # a file from elsewhere still finds the tree's headers
+            src, extra = os.environ["CSM_VARIANT_FILE"], ["-I" + CSRC, *extra]
+        cmd = compile_cmd(src, obj, extra, name)
+        print(" ".join(cmd), file=sys.stderr)
+        return subprocess.run(cmd).returncode
     print(build(verbose=True))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(_main(sys.argv[1:]))

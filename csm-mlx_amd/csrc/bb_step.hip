@@ -42,10 +42,7 @@ constexpr unsigned SPIN_LIMIT = 1u << 22; // ~0.1 s of s_sleep per hand-off befo
 // E3, E5: every workgroup reads every granule) are written in REP replicas, workgroup w reading
 // replica w % REP (dec_frame.hip: fewer readers per granule; speed only, never correctness).
 // Measured: 581-584 us (REP 1 / 8) -> 569 us (REP 4) per row (profiles/r03_ab_replicas.txt).
-#ifndef BB_REP
-#define BB_REP 4
-#endif
-constexpr int REP = BB_REP;
+constexpr int REP = 4;
 __host__ __device__ constexpr size_t rs_of(size_t per) { return (per + 511) / 512 * 512 + 32; }
 constexpr size_t G_QKV = 0;                                   // [2][QKV]
 constexpr size_t G_ATT = G_QKV + 2 * QKV;                     // [2][REP][rs(D)]
@@ -100,54 +97,23 @@ struct Ctx {
   }
 };
 
-// BB_PROBE_DELAY: sleeps before the first probe of a hand-off wait (the producers are still working
+// Sleeps (s_sleep units) before the first probe of a hand-off wait: the producers are still working
 // when a workgroup starts waiting; an early probe returns stale and its re-polls load the lines every
-// workgroup polls -- dec_frame.hip measured -6 % per frame from the same delay).
-#ifndef BB_PROBE_DELAY
-#define BB_PROBE_DELAY 32
-#endif
-// BB_DELAY_E2: the E2 wait of the 224 workgroups that run no attention (they wait the whole attention)
-#ifndef BB_ATTN_LATE_PF
-#define BB_ATTN_LATE_PF 0
-#endif
-#ifndef BB_EARLY_MQ2
-#define BB_EARLY_MQ2 1
-#endif
-#ifndef BB_DELAY_E2
-#define BB_DELAY_E2 BB_PROBE_DELAY
-#endif
-template <int DELAY = BB_PROBE_DELAY>
-__device__ __forceinline__ void probe_delay() {
-  if (DELAY > 0) __builtin_amdgcn_s_sleep(DELAY);
-}
-__device__ __forceinline__ bool spin_fail(Ctx& c, unsigned spin) {
-  if (spin >= SPIN_LIMIT || ((spin & 255) == 255 && __hip_atomic_load(c.p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-    __hip_atomic_store(c.p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-  }
-  return false;
-}
+// workgroup polls (profiles/r03_ab_probe_delay.txt: 551 -> 501-511 us per row).
+constexpr int PROBE_DELAY = 32;
+// the E2 wait of the 224 workgroups that run no attention (they wait the whole attention): no longer
+// delay measured better
+constexpr int DELAY_E2 = PROBE_DELAY;
+__device__ __forceinline__ bool spin_fail(Ctx& c, unsigned spin) { return handoff::spin_fail(c.p.err, SPIN_LIMIT, spin); }
 
-// Wait until granules [0, n) of buf carry this hand-off's tag; values -> out (LDS).
-template <int GPT, int DELAY = BB_PROBE_DELAY>
+// Wait until granules [0, n) of buf carry this hand-off's tag; values -> out (LDS).  One 8-B load per
+// granule (thread t: granules t + NT u): the bf16 kernel's E2 wait.  Not handoff.h poll_granules: an
+// unused entry counts as current without a load here.
+template <int GPT, int DELAY = PROBE_DELAY>
 __device__ __forceinline__ void gather(Ctx& c, const u64* buf, int n, float* out) {
-#if BB_PAIR16
-  // granule pairs 2t + D/2 h (n == D: every pair whole)
-  const unsigned tag = c.tag();
-  const int poff[GPT / 2] = {2 * c.tid, D / 2 + 2 * c.tid};
-  poll_pairs<GPT / 2, DELAY, 1>(buf, 0x7fffffff, poff, tag, [&](unsigned spin) { return spin_fail(c, spin); },
-                                [&](const u32x4_t (&g)[GPT / 2]) {
-#pragma unroll
-    for (int h = 0; h < GPT / 2; ++h)
-      *reinterpret_cast<float2*>(&out[poff[h]]) = make_float2(__uint_as_float(g[h].x), __uint_as_float(g[h].z));
-  });
-  c.stamp(c.e + 1);
-  __syncthreads();
-  (void)n;
-#else
   const unsigned tag = c.tag();
   u64 g[GPT];
-  probe_delay<DELAY>();
+  __builtin_amdgcn_s_sleep(DELAY);
 #pragma unroll
   for (int u = 0; u < GPT; ++u) {
     const int i = c.tid + u * NT;
@@ -172,22 +138,12 @@ __device__ __forceinline__ void gather(Ctx& c, const u64* buf, int n, float* out
     if (i < n) out[i] = __uint_as_float((unsigned)g[u]);
   }
   __syncthreads();
-#endif
 }
 
-// BB_PAIR16 (as dec_frame.hip DF_PAIR16): the x / attention-output hand-offs and the down partials
-// polled as granule pairs, one 16-B load each; thread t then owns elements 2t, 2t + 1, 1024 + 2t,
-// 1024 + 2t + 1 of a row (else t + 512 j)
-#ifndef BB_PAIR16
-#define BB_PAIR16 1
-#endif
-// BB_E4_16: each thread's down rows are el(k) and its partials go out two granules per 16-B store
-#ifndef BB_E4_16
-#define BB_E4_16 0
-#endif
-__device__ __forceinline__ int el(const Ctx& c, int j) {
-  return BB_PAIR16 ? (j >> 1) * (D / 2) + 2 * c.tid + (j & 1) : c.tid + j * NT;
-}
+// The x hand-offs and the down partials are polled as granule pairs, one 16-B load each (as
+// dec_frame.hip; profiles/r03_ab_pairs.txt): thread t owns elements el(j) = 2t, 2t + 1, 1024 + 2t,
+// 1024 + 2t + 1 of a row.
+__device__ __forceinline__ int el(const Ctx& c, int j) { return (j >> 1) * (D / 2) + 2 * c.tid + (j & 1); }
 // xn[k] = x[k] * rsqrt(mean(x^2) + eps) * nw[k]; nw elements el(j) fetched a phase ahead
 struct Nw { float v[D / NT]; };
 __device__ __forceinline__ Nw nw_fetch(const Ctx& c, const float* nw) {
@@ -211,20 +167,16 @@ __device__ __forceinline__ void rms(Ctx& c, const Nw& nw, float* out) {
   __syncthreads();
 }
 
-// Folded RMSNorm (BB_FOLD, as dec_frame.hip): an x hand-off is gathered into x and xn = x * nw (the
-// next consumer's norm weight) with per-wave sums of squares; consumers dot against the
-// un-normalised xn and scale by rsqrt(mean(x^2) + eps) -- one barrier and one serial pass fewer.
-#ifndef BB_FOLD
-#define BB_FOLD 1
-#endif
+// Folded RMSNorm (as dec_frame.hip; profiles/r03_ab_fold.txt): an x hand-off is gathered into x and
+// xn = x * nw (the next consumer's norm weight) with per-wave sums of squares; consumers dot against
+// the un-normalised xn and scale by rsqrt(mean(x^2) + eps) -- one barrier and one serial pass fewer.
 __device__ __forceinline__ void gather_x(Ctx& c, const u64* buf, const Nw& nw) {
   constexpr int GPT = D / NT;
   const unsigned tag = c.tag();
   float sq = 0.f;
-#if BB_PAIR16
   const int poff[GPT / 2] = {2 * c.tid, D / 2 + 2 * c.tid};
-  poll_pairs<GPT / 2, BB_PROBE_DELAY, 1>(buf, 0x7fffffff, poff, tag, [&](unsigned spin) { return spin_fail(c, spin); },
-                                         [&](const u32x4_t (&g)[GPT / 2]) {
+  poll_pairs<GPT / 2, PROBE_DELAY, 1>(buf, 0x7fffffff, poff, tag, [&](unsigned spin) { return spin_fail(c, spin); },
+                                      [&](const u32x4_t (&g)[GPT / 2]) {
 #pragma unroll
     for (int h = 0; h < GPT / 2; ++h) {
       const float v0 = __uint_as_float(g[h].x), v1 = __uint_as_float(g[h].z);
@@ -235,30 +187,6 @@ __device__ __forceinline__ void gather_x(Ctx& c, const u64* buf, const Nw& nw) {
     }
   });
   c.stamp(c.e + 1);
-#else
-  u64 g[GPT];
-  probe_delay();
-#pragma unroll
-  for (int u = 0; u < GPT; ++u) g[u] = gload(buf + c.tid + u * NT);
-  for (unsigned spin = 0;; ++spin) {
-    bool ok = true;
-#pragma unroll
-    for (int u = 0; u < GPT; ++u) ok &= (unsigned)(g[u] >> 32) == tag;
-    if (ok || spin_fail(c, spin)) break;
-    __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-    for (int u = 0; u < GPT; ++u)
-      if ((unsigned)(g[u] >> 32) != tag) g[u] = gload(buf + c.tid + u * NT);
-  }
-  c.stamp(c.e + 1);
-#pragma unroll
-  for (int u = 0; u < GPT; ++u) {
-    const float v = __uint_as_float((unsigned)g[u]);
-    c.L.x[c.tid + u * NT] = v;
-    c.L.xn[c.tid + u * NT] = v * nw.v[u];
-    sq = fmaf(v, v, sq);
-  }
-#endif
   sq = wave_sum(sq);
   if (c.lane == 0) c.L.sq[c.wave] = sq;
   __syncthreads();
@@ -300,8 +228,8 @@ __device__ __forceinline__ void load_mq(Ctx& c, int l, int Q, WMq& r) {
   // chunk 4w + Q of [F/8][D][8]: row n at byte (n * 8) * 2
   const bf16_t* d = c.p.wdc[l] + (size_t)(4 * c.w + Q) * D * 8;
 #pragma unroll
-  for (int k = 0; k < 4; ++k)  // rows el(k): 2t + (k & 1) + 1024 (k >> 1) with BB_E4_16, else t + 512 k
-    r.d[k] = BB_E4_16 ? bload<2>(d, c.tid * 32, ((k >> 1) * (D / 2) + (k & 1)) * 16) : bload<2>(d, c.tid * 16, k * NT * 8 * 2);
+  for (int k = 0; k < 4; ++k)  // rows t + 512 k
+    r.d[k] = bload<2>(d, c.tid * 16, k * NT * 8 * 2);
 }
 
 // per-row partial sums of a (half, chunk)-split projection: wave partials -> wsum[wave][i]
@@ -371,8 +299,9 @@ __device__ __forceinline__ void kv_pass_load(const Ctx& c, const float* K, const
 }
 
 // Attention of query head a (WG a < NATT), in two parts so the caller can issue its weight prefetch
-// between them (BB_ATTN_LATE_PF: after the E1 poll and the first pass's K / V loads, so neither
-// queues behind it):
+// between them.  (The prefetch goes BEFORE attn_begin: issued after the E1 poll and the first pass's
+// K / V loads it cut E1 on these workgroups 7.1 -> 3.4 us but cost E2 +2.9 us, 524 vs 501 us per row;
+// DESIGN.md, round 3 "tried, not kept".)
 // attn_begin: the E1 wait (q_a, k_g, v_g) and the first pass's K / V loads.
 __device__ __forceinline__ void attn_begin(Ctx& c, int l, int pos, KvPass& kp) {
   const int a = c.w, g = a / (HQ / HKV);
@@ -382,7 +311,7 @@ __device__ __forceinline__ void attn_begin(Ctx& c, int l, int pos, KvPass& kp) {
     if (c.tid < 3 * HD) {
       const int part = c.tid / HD, d = c.tid % HD;
       const int idx = part == 0 ? a * HD + d : (part == 1 ? HQ * HD + g * HD + d : (HQ + HKV) * HD + g * HD + d);
-      probe_delay();
+      __builtin_amdgcn_s_sleep(PROBE_DELAY);
       u64 v = gload(buf + idx);
       for (unsigned spin = 0; (unsigned)(v >> 32) != tag; ++spin) {
         if (spin_fail(c, spin)) break;
@@ -508,11 +437,9 @@ __device__ __forceinline__ void phase_reduce(Ctx& c) {
   const unsigned tag = c.tag();
   const u64* g = c.buf(G_PART, (size_t)NWG * D);
   const int v = c.tid >> 1, half = c.tid & 1;
-  const u64* src = g + (size_t)v * D + 8 * c.w + 4 * half;
-#if BB_PAIR16
   const int poff[2] = {v * D + 8 * c.w + 4 * half, v * D + 8 * c.w + 4 * half + 2};
-  poll_pairs<2, BB_PROBE_DELAY, 1>(g, 0x7fffffff, poff, tag, [&](unsigned spin) { return spin_fail(c, spin); },
-                                   [&](const u32x4_t (&q)[2]) {
+  poll_pairs<2, PROBE_DELAY, 1>(g, 0x7fffffff, poff, tag, [&](unsigned spin) { return spin_fail(c, spin); },
+                                [&](const u32x4_t (&q)[2]) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       c.L.red[4 * half + 2 * h][v] = __uint_as_float(q[h].x);
@@ -520,26 +447,6 @@ __device__ __forceinline__ void phase_reduce(Ctx& c) {
     }
   });
   c.stamp(c.e + 1);
-  (void)src;
-#else
-  u64 q[4];
-  probe_delay();
-#pragma unroll
-  for (int u = 0; u < 4; ++u) q[u] = gload(src + u);
-  for (unsigned spin = 0;; ++spin) {
-    bool ok = true;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) ok &= (unsigned)(q[u] >> 32) == tag;
-    if (ok || spin_fail(c, spin)) break;
-    __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if ((unsigned)(q[u] >> 32) != tag) q[u] = gload(src + u);
-  }
-  c.stamp(c.e + 1);
-#pragma unroll
-  for (int u = 0; u < 4; ++u) c.L.red[4 * half + u][v] = __uint_as_float((unsigned)q[u]);
-#endif
   __syncthreads();
   ++c.e;  // the x hand-off that follows
   {
@@ -617,8 +524,8 @@ __device__ __forceinline__ void half_group_sums(Ctx& c, const float (&pair)[2], 
 __device__ __forceinline__ void gather_x4(Ctx& c, const u64* buf, const Nw& nw) {
   const int poff[2] = {2 * c.tid, D / 2 + 2 * c.tid};
   float sq = 0.f, pr[2];
-  poll_pairs<2, BB_PROBE_DELAY, 1>(buf, 0x7fffffff, poff, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); },
-                                   [&](const u32x4_t (&g)[2]) {
+  poll_pairs<2, PROBE_DELAY, 1>(buf, 0x7fffffff, poff, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); },
+                                [&](const u32x4_t (&g)[2]) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const float v0 = __uint_as_float(g[h].x), v1 = __uint_as_float(g[h].z);
@@ -655,7 +562,7 @@ __device__ __forceinline__ void stage_x4(Ctx& c, const Nw& nw) {
   __syncthreads();
 }
 // the attention output hand-off (E2) -> aq (padded), ah
-template <int DELAY = BB_PROBE_DELAY>
+template <int DELAY = PROBE_DELAY>
 __device__ __forceinline__ void gather_att4(Ctx& c, const u64* buf) {
   const int poff[2] = {2 * c.tid, D / 2 + 2 * c.tid};
   float pr[2];
@@ -772,7 +679,7 @@ __global__ __launch_bounds__(NT, 1) void bb_step_q4_kernel(BbStepArgs p) {
       load_m4(c, l, wm);
     }
     if (attn_wg) gather_att4(c, c.rbuf(G_ATT, D));   // E2
-    else gather_att4<BB_DELAY_E2>(c, c.rbuf(G_ATT, D));
+    else gather_att4<DELAY_E2>(c, c.rbuf(G_ATT, D));
     ++c.e;
     c.refresh();
     phase_o4(c, wo);                                  // -> E3
@@ -823,7 +730,7 @@ __global__ __launch_bounds__(NT, 1) void bb_step_kernel(BbStepArgs p) {
   for (int l = 0; l < NL; ++l) {
     c.refresh();
     // layers >= 1 (folded): the previous layer's E5 gather already wrote xn = x * n1
-    const bool fold1 = BB_FOLD && l > 0;
+    const bool fold1 = l > 0;
     if (!fold1) rms(c, nw1, L.xn);
     phase_qkv(c, l, pos, wq, fold1);                  // -> E1
     ++c.e;                                            // E1 is read by the attention workgroups only
@@ -834,81 +741,55 @@ __global__ __launch_bounds__(NT, 1) void bb_step_kernel(BbStepArgs p) {
     // quarters after the attention, the third quarter during E3, the next layer's first quarter
     // during E4 / E5 -- none faster.
     KvPass kp;
-    if (attn_wg && BB_ATTN_LATE_PF) attn_begin(c, l, pos, kp);  // waits E1, first K / V pass in flight
     load_o(c, l, wo);
     load_mq(c, l, 0, mq[0]);
     if (!attn_wg) {
       load_mq(c, l, 1, mq[1]);
-      // BB_EARLY_MQ2: the 224 workgroups without attention wait the whole attention at E2, so their
-      // third quarter streams there too instead of inside the MLP
-      if (BB_EARLY_MQ2) load_mq(c, l, 2, mq[2]);
+      // the 224 workgroups without attention wait the whole attention at E2, so their third quarter
+      // streams there too instead of inside the MLP (501-511 -> 493-501 us per row)
+      load_mq(c, l, 2, mq[2]);
     }
     const Nw nw2 = nw_fetch(c, p.n2[l]);
     if (attn_wg) {
-      if (!BB_ATTN_LATE_PF) attn_begin(c, l, pos, kp);
+      attn_begin(c, l, pos, kp);                      // waits E1, first K / V pass in flight
       attn_rest(c, l, pos, kp);                       // -> E2
       load_mq(c, l, 1, mq[1]);
     }
     if (attn_wg) gather<D / NT>(c, c.rbuf(G_ATT, D), D, L.att);  // E2
-    else gather<D / NT, BB_DELAY_E2>(c, c.rbuf(G_ATT, D), D, L.att);
+    else gather<D / NT, DELAY_E2>(c, c.rbuf(G_ATT, D), D, L.att);
     ++c.e;
     c.refresh();
     phase_o(c, wo);                                   // -> E3
     if (l + 1 < NL) load_q(c, l + 1, wq);
-#if BB_FOLD
     gather_x(c, c.rbuf(G_X, D), nw2);                 // E3 -> x, xn = x * n2
     const float rs2 = row_rs(c);
-#else
-    gather<D / NT>(c, c.rbuf(G_X, D), D, L.x);         // E3
-    const float rs2 = 1.f;
-#endif
     ++c.e;
     c.refresh();
-    if (!BB_FOLD) rms(c, nw2, L.xn);
     float acc[4];
     phase_mq<0>(c, mq[0], acc, rs2);
-    if (attn_wg || !BB_EARLY_MQ2) load_mq(c, l, 2, mq[2]);
+    if (attn_wg) load_mq(c, l, 2, mq[2]);
     phase_mq<1>(c, mq[1], acc, rs2);
     load_mq(c, l, 3, mq[3]);
     phase_mq<2>(c, mq[2], acc, rs2);
     phase_mq<3>(c, mq[3], acc, rs2);
     {
       u64* g = c.buf(G_PART, (size_t)NWG * D) + (size_t)c.w * D;
-      if (BB_E4_16) {  // rows 2t, 2t + 1 (+ 1024): two granules per 16-B sc1 store   -> E4
-        const unsigned tg = c.tag();
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(g, 0, 0x7fffffff, 0x00020000);
+      // rows t + 512 k, one 8-B store per granule (not dec_frame.hip's two granules per 16-B store)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const u32x4_t v = {__float_as_uint(acc[2 * h]), tg, __float_as_uint(acc[2 * h + 1]), tg};
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs, (h * (D / 2) + 2 * c.tid) * 8, 0, 16);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) gput(g + c.tid + NT * k, acc[k], c.tag());   // -> E4
-      }
+      for (int k = 0; k < 4; ++k) gput(g + c.tid + NT * k, acc[k], c.tag());   // -> E4
     }
     nw1 = nw_fetch(c, l + 1 < NL ? p.n1[l + 1] : p.norm);
     c.refresh();
     phase_reduce(c);                                  // waits E4, -> E5
-#if BB_FOLD
     gather_x(c, c.rbuf(G_X, D), nw1);                 // E5 -> x, xn = x * (next n1 | final norm)
-#else
-    gather<D / NT>(c, c.rbuf(G_X, D), D, L.x);         // E5
-#endif
     ++c.e;
   }
   // final norm of the last row -> h_last (generation.py:42 reads norm(h[:, -1]))
   c.refresh();
-#if BB_FOLD
   if (c.w == 0) {
     const float rs = row_rs(c);
     for (int k = c.tid; k < D; k += NT) p.h_last[k] = L.xn[k] * rs;
   }
-#else
-  rms(c, nw1, L.xn);
-  if (c.w == 0)
-    for (int k = c.tid; k < D; k += NT) p.h_last[k] = L.xn[k];
-#endif
   c.stamp(BB_STEP_STAMPS - 1);
   if (c.w == 0 && c.tid == 0) __hip_atomic_store(p.epoch, c.tag0 - 1u + (unsigned)c.e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -1,5 +1,5 @@
 // Persistent frame decoder: codebook0_head + the 31 depth-decoder steps of one frame
-// (/root/reference/csm_mlx/generation.py:42-90) in ONE launch, batch 1, greedy, bf16 weights.
+// (the reference's csm_mlx/generation.py:42-90) in ONE launch, batch 1, greedy, bf16 weights.
 //
 // Why: at batch 1 the depth decoder is a chain of 31 x (4 layers x 5 projections + attention + head)
 // dependent launches of 2-34 MB each; every launch pays a kernel boundary plus its own ramp and
@@ -127,10 +127,7 @@ namespace {
 // The reduce-scatter region (G_PART: each granule has one reader) is not replicated.  Measured
 // (profiles/r03_ab_replicas.txt): 2394 -> 2325 us per frame at REP 4 or 8 with the replica stores
 // spread over lanes (stored serially by one lane, REP 8 cost more on the publish than it saved).
-#ifndef DF_REP
-#define DF_REP 4
-#endif
-constexpr int REP = DF_REP;
+constexpr int REP = 4;
 __host__ __device__ constexpr size_t rs_of(size_t per) { return (per + 511) / 512 * 512 + 32; }
 constexpr size_t G_X = 0;                                               // [2][REP][rs(MAXM*D)] x slices
 constexpr size_t G_QKV = G_X + 2 * REP * rs_of(MAXM * D);               // [2][REP][rs(MAXM*QKV)]
@@ -177,94 +174,31 @@ struct Ctx {
   }
 };
 
-// Hand-off waits (handoff.h poll_granules): DF_POLL2 keeps two probes in flight, DF_POLL_GAP
-// sleeps apart.
-#ifndef DF_DN_AFTER_E1
-#define DF_DN_AFTER_E1 0
-#endif
-#ifndef DF_DN_EARLY
-#define DF_DN_EARLY 0
-#endif
-#ifndef DF_GU_E45
-#define DF_GU_E45 0   // gate/up rows per wave of the next layer fetched during E4 / E5 (<= GU_EARLY)
-#endif
-#ifndef DF_POLL2
-#define DF_POLL2 0
-#endif
-#ifndef DF_PROBE_DELAY
-#define DF_PROBE_DELAY 16
-#endif
-#ifndef DF_REPOLL
-#define DF_REPOLL 2
-#endif
-// per hand-off kind (E1 q|k|v, E3 / E5 x, E4 down partials, E6 arg-max keys), default DF_PROBE_DELAY
-#ifndef DF_DELAY_E1
-#define DF_DELAY_E1 DF_PROBE_DELAY
-#endif
-#ifndef DF_DELAY_E3
-#define DF_DELAY_E3 DF_PROBE_DELAY
-#endif
-#ifndef DF_DELAY_E4
-#define DF_DELAY_E4 DF_PROBE_DELAY
-#endif
-#ifndef DF_DELAY_E5
-#define DF_DELAY_E5 40
-#endif
-#ifndef DF_DELAY_E6
-#define DF_DELAY_E6 DF_PROBE_DELAY
-#endif
-#ifndef DF_POLL_GAP
-#define DF_POLL_GAP 8
-#endif
-__device__ __forceinline__ bool spin_fail(Ctx& c, unsigned spin) {
-  if (spin >= SPIN_LIMIT || ((spin & 255) == 255 && __hip_atomic_load(c.p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-    __hip_atomic_store(c.p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-  }
-  return false;
-}
+// Hand-off waits (handoff.h poll_pairs / poll_granules), in s_sleep units.
+// Sleeps before the first probe of a wait: a workgroup starts polling right after its own publish,
+// while most producers are still working (profiles/r03_ab_probe_delay.txt: -6 % per frame).
+constexpr int PROBE_DELAY = 16;
+// per hand-off kind: E5 (x after the reduce-scatter, nothing queued before its poll) wants 40; E1
+// (q|k|v), E3 (x), E4 (down partials) and E6 (arg-max keys) poll behind the layer's prefetch, where 40
+// cost +50-90 us per frame (profiles/r03_ab_probe_delay.txt)
+constexpr int DELAY_E1 = PROBE_DELAY, DELAY_E3 = PROBE_DELAY, DELAY_E4 = PROBE_DELAY, DELAY_E5 = 40, DELAY_E6 = PROBE_DELAY;
+// sleeps between re-polls of a stale probe: the hand-off lines are the contended resource, so fewer
+// probes, not faster ones (profiles/r03_ab_poll.txt)
+constexpr int REPOLL = 2;
+
+__device__ __forceinline__ bool spin_fail(Ctx& c, unsigned spin) { return handoff::spin_fail(c.p.err, SPIN_LIMIT, spin); }
 // use(x): the lane-local consumption of the matched probe
-template <int GPT, int DELAY = DF_PROBE_DELAY, typename F>
+template <int GPT, int DELAY = PROBE_DELAY, typename F>
 __device__ __forceinline__ void poll(Ctx& c, const u64* base, const int (&off)[GPT], const bool (&val)[GPT], F&& use) {
-  poll_granules<GPT, DF_POLL2 != 0, DF_POLL_GAP, DELAY, DF_REPOLL>(base, off, val, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); }, use);
+  poll_granules<GPT, DELAY, REPOLL>(base, off, val, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); }, use);
   c.stamp();
 }
 
 // Wait until granules [0, n) of buf carry `tag`; values -> out (LDS).  Threads take granules
-// tid, tid + NT, ... (at most GPT each).
+// tid, tid + NT, ... (at most GPT each), one 8-B load per granule: the frame start's x row and the
+// logits of top-k sampling, once per frame or per sampled head, not per layer.
 template <int GPT>
 __device__ __forceinline__ void gather(Ctx& c, const u64* buf, int n, float* out) {
-#if DF_PAIR16
-  // granule pairs (2i, 2i + 1), i = tid, tid + NT, ...; a granule past n (odd n) counts as current
-  constexpr int GPP = (GPT + 1) / 2;
-  const int np = (n + 1) / 2;
-  int poff[GPP];
-#pragma unroll
-  for (int u = 0; u < GPP; ++u) poff[u] = 2 * min(c.tid + u * NT, np - 1);
-  const unsigned tag = c.tag();
-  if (DF_PROBE_DELAY > 0) __builtin_amdgcn_s_sleep(DF_PROBE_DELAY);
-  auto cur1 = [&](const u32x4_t& x, int i) { return x.y == tag && (i + 1 >= n || x.w == tag); };
-  u32x4_t g[GPP];
-#pragma unroll
-  for (int u = 0; u < GPP; ++u) g[u] = sc1_load16(buf, poff[u] * 8, 0x7fffffff);
-  for (unsigned spin = 0;; ++spin) {
-    bool ok = true;
-#pragma unroll
-    for (int u = 0; u < GPP; ++u) ok &= cur1(g[u], poff[u]);
-    if (ok || spin_fail(c, spin)) break;
-    __builtin_amdgcn_s_sleep(DF_REPOLL);
-#pragma unroll
-    for (int u = 0; u < GPP; ++u)
-      if (!cur1(g[u], poff[u])) g[u] = sc1_load16(buf, poff[u] * 8, 0x7fffffff);
-  }
-  c.stamp();
-#pragma unroll
-  for (int u = 0; u < GPP; ++u)
-    if (c.tid + u * NT < np) {
-      out[poff[u]] = __uint_as_float(g[u].x);
-      if (poff[u] + 1 < n) out[poff[u] + 1] = __uint_as_float(g[u].z);
-    }
-#else
   int off[GPT];
   bool val[GPT];
 #pragma unroll
@@ -277,27 +211,22 @@ __device__ __forceinline__ void gather(Ctx& c, const u64* buf, int n, float* out
     for (int u = 0; u < GPT; ++u)
       if (val[u]) out[off[u]] = __uint_as_float((unsigned)g[u]);
   });
-#endif
   __syncthreads();
 }
 
-// xn[m][k] = x[m][k] * rsqrt(mean(x^2) + eps) * nw[k] for rows m < M (every WG computes the same)
-// RMSNorm weight elements tid and tid + 512 (every element a thread scales), fetched a phase ahead
-// DF_PAIR16: x hand-offs (E3 / E5) and the down partials (E4) polled as granule pairs, one 16-B load
-// each (thread t owns elements 2t, 2t + 1 of a row instead of t, t + NT)
-#ifndef DF_PAIR16
-#define DF_PAIR16 1
-#endif
-__device__ __forceinline__ int el0(const Ctx& c) { return DF_PAIR16 ? 2 * c.tid : c.tid; }
-__device__ __forceinline__ int el1(const Ctx& c) { return DF_PAIR16 ? 2 * c.tid + 1 : c.tid + NT; }
-__device__ __forceinline__ float2 nw_fetch(const Ctx& c, const float* nw) { return make_float2(nw[el0(c)], nw[el1(c)]); }
+// The x hand-offs (E3 / E5) and the down partials (E4) travel as granule pairs, one 16-B load each:
+// thread t owns elements 2t, 2t + 1 of a row (profiles/r03_ab_pairs.txt).
+// RMSNorm weight elements 2 tid and 2 tid + 1 (every element a thread scales), fetched a phase ahead
+__device__ __forceinline__ float2 nw_fetch(const Ctx& c, const float* nw) { return make_float2(nw[2 * c.tid], nw[2 * c.tid + 1]); }
 
+// xn[m][k] = x[m][k] * rsqrt(mean(x^2) + eps) * nw[k] for rows m < M (every WG computes the same):
+// step 1's layer 0, whose rows come from the frame start and not from an x hand-off
 template <int M>
-__device__ __forceinline__ void rms_rows(Ctx& c, float2 nw, int m0 = 0) {
-  static_assert(D == 2 * NT, "a thread scales elements tid and tid + NT of each row");
+__device__ __forceinline__ void rms_rows(Ctx& c, float2 nw) {
+  static_assert(D == 2 * NT, "a thread scales elements 2 tid and 2 tid + 1 of each row");
   // sum of squares: wave m sums row m in a fixed order
   if (c.wave < M) {
-    const float* x = c.L.x[m0 + c.wave];
+    const float* x = c.L.x[c.wave];
     float s = 0.f;
     for (int k = c.lane; k < D; k += 64) s = fmaf(x[k], x[k], s);
     s = wave_sum(s);
@@ -306,37 +235,26 @@ __device__ __forceinline__ void rms_rows(Ctx& c, float2 nw, int m0 = 0) {
   __syncthreads();
   for (int m = 0; m < M; ++m) {
     const float r = rsqrtf(c.L.wsum[0][m] / (float)D + c.p.eps);
-    c.L.xn[m][el0(c)] = c.L.x[m0 + m][el0(c)] * r * nw.x;
-    c.L.xn[m][el1(c)] = c.L.x[m0 + m][el1(c)] * r * nw.y;
+    c.L.xn[m][2 * c.tid] = c.L.x[m][2 * c.tid] * r * nw.x;
+    c.L.xn[m][2 * c.tid + 1] = c.L.x[m][2 * c.tid + 1] * r * nw.y;
   }
   __syncthreads();
 }
 
-// Folded RMSNorm (DF_FOLD): an x hand-off is gathered straight into x and into xn = x * nw (the next
+// Folded RMSNorm: an x hand-off is gathered straight into x and into xn = x * nw (the next
 // consumer's norm weight) with per-wave sums of squares; the consumer dots against the un-normalised
 // xn and scales its results by rsqrt(mean(x^2) + eps) -- one barrier and one pass over the rows
-// fewer per norm (the batched path's xs.h does the same: row scale after the dot product).
-#ifndef DF_FOLD
-#define DF_FOLD 1
-#endif
+// fewer per norm (the batched path's xs.h does the same: row scale after the dot product;
+// profiles/r03_ab_fold.txt).
 template <int M, int DELAY>
 __device__ __forceinline__ void gather_x(Ctx& c, const u64* buf, float2 nw) {
-  static_assert(D == 2 * NT, "granule tid + NT u is element (u / 2, tid + NT (u % 2))");
-  constexpr int GPT = M * D / NT;
-  int off[GPT];
-  bool val[GPT];
-#pragma unroll
-  for (int u = 0; u < GPT; ++u) {
-    off[u] = c.tid + u * NT;
-    val[u] = true;
-  }
+  static_assert(D == 2 * NT, "pair tid of row m is elements 2 tid, 2 tid + 1");
   float sq[MAXM];
-#if DF_PAIR16
   int poff[M];
 #pragma unroll
   for (int m = 0; m < M; ++m) poff[m] = m * D + 2 * c.tid;
-  poll_pairs<M, DELAY, DF_REPOLL>(buf, 0x7fffffff, poff, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); },
-                                  [&](const u32x4_t (&g)[M]) {
+  poll_pairs<M, DELAY, REPOLL>(buf, 0x7fffffff, poff, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); },
+                               [&](const u32x4_t (&g)[M]) {
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       const float v0 = __uint_as_float(g[m].x), v1 = __uint_as_float(g[m].z);
@@ -346,20 +264,6 @@ __device__ __forceinline__ void gather_x(Ctx& c, const u64* buf, float2 nw) {
     }
   });
   c.stamp();
-  (void)off; (void)val;
-#else
-  poll<GPT, DELAY>(c, buf, off, val, [&](const u64 (&g)[GPT]) {
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      const float v0 = __uint_as_float((unsigned)g[2 * m]), v1 = __uint_as_float((unsigned)g[2 * m + 1]);
-      c.L.x[m][c.tid] = v0;
-      c.L.x[m][c.tid + NT] = v1;
-      c.L.xn[m][c.tid] = v0 * nw.x;
-      c.L.xn[m][c.tid + NT] = v1 * nw.y;
-      sq[m] = fmaf(v1, v1, v0 * v0);
-    }
-  });
-#endif
 #pragma unroll
   for (int m = 0; m < M; ++m) {
     const float t = wave_sum(sq[m]);
@@ -378,11 +282,11 @@ __device__ __forceinline__ float row_rs(const Ctx& c, int m) {
 // ---- weight slices held in registers (issued ahead of use)
 struct WQkv { u32x4_t a, b; };      // waves 0..5: row 6w+wave, chunks lane / lane+64
 struct WO { u32x4_t a; };            // row 4w + wave/2, chunk (wave&1)*64 + lane
-#ifndef GU_EARLY
-#define GU_EARLY 4  // gate/up rows per wave fetched before the attention (the rest after o_proj)
-#endif
+// gate/up rows per wave (of 8) fetched before the attention, the rest after o_proj: 2 / 3 / 4 / 5 / 6
+// gave 2418 / 2392 / 2397-2407 / 2428 / 2477 us per frame (no profiles/ file)
+constexpr int GU_EARLY = 4;
 struct WGu { u32x4_t a[8][2]; };     // rows 64w + 8*wave + r, chunks lane / lane+64
-struct WDn { u32x4_t a[2][2][2]; };  // [row t / t+512][chunk 2w+q][16-B half]
+struct WDn { u32x4_t a[2][2][2]; };  // [row 2t / 2t+1][chunk 2w+q][16-B half]
 struct WHd { u32x4_t a[2]; u32x4_t x[2]; };  // head row 8w+wave (+ row 2048+w for wave 0, w < 3)
 
 __device__ __forceinline__ void load_qkv(Ctx& c, int l, WQkv& r) {
@@ -407,22 +311,16 @@ __device__ __forceinline__ void load_gu(Ctx& c, int l, WGu& r) {
     r.a[i][1] = bload(base, v, i * D * 2 + 1024);
   }
 }
-// DF_E4_16: thread t computes down rows 2t, 2t + 1 (not t, t + 512) and publishes both partials in
-// one 16-B sc1 store (two granules, each with its own tag)
-#ifndef DF_E4_16
-#define DF_E4_16 1
-#endif
-#ifndef DF_TAB16
-#define DF_TAB16 1
-#endif
+// thread t computes down rows 2t, 2t + 1 and publishes both partials in one 16-B sc1 store (two
+// granules, each with its own tag)
 __device__ __forceinline__ void load_dn(Ctx& c, int l, WDn& r) {
   const bf16_t* base = c.p.wdc[l] + (size_t)(2 * c.w) * D * 16;
-  const int v = DF_E4_16 ? c.tid * 16 * 2 * 2 : c.tid * 16 * 2;
+  const int v = c.tid * 16 * 2 * 2;
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      const int so = DF_E4_16 ? (q * D * 16 + s * 16) * 2 : (q * D * 16 + 512 * s * 16) * 2;
+      const int so = (q * D * 16 + s * 16) * 2;
       r.a[s][q][0] = bload(base, v, so);
       r.a[s][q][1] = bload(base, v, so + 16);
     }
@@ -579,23 +477,9 @@ __device__ __forceinline__ void kv_store(Ctx& c, int pos0, const KvRegs& r) {
   }
 }
 
-// The step's new K / V rows (positions pos0 .. pos0+M-1, gathered in L.qkv) appended to the LDS
-// history, so the attention reads every key from one array.
-template <int M>
-__device__ __forceinline__ void kv_append(Ctx& c, int pos0) {
-  for (int idx = c.tid; idx < M * HKV * HD; idx += NT) {
-    const int m = idx / (HKV * HD), r = idx % (HKV * HD), g = r / HD, d = r % HD;
-    c.L.Ks[g][pos0 + m][d] = c.L.qkv[m][HQ * HD + r];
-    c.L.Vs[g][pos0 + m][d] = c.L.qkv[m][(HQ + HKV) * HD + r];
-  }
-}
-
-// DF_KVDIRECT: the q | k | v hand-off (and layer 0's table row) is written straight to its places --
-// q to L.qkv, the new k / v rows into the LDS history at pos0 + m -- so no kv_append pass and one
-// barrier fewer before the attention.
-#ifndef DF_KVDIRECT
-#define DF_KVDIRECT 1
-#endif
+// The q | k | v hand-off (and layer 0's table row) is written straight to its places -- q to L.qkv,
+// the new k / v rows into the LDS history at pos0 + m -- so the attention reads every key from one
+// array with no append pass and no barrier of its own.
 __device__ __forceinline__ void qkv_place(Ctx& c, int m, int r, int pos0, float v) {
   if (r < HQ * HD) c.L.qkv[m][r] = v;
   else if (r < (HQ + HKV) * HD) c.L.Ks[(r - HQ * HD) / HD][pos0 + m][r % HD] = v;
@@ -603,21 +487,12 @@ __device__ __forceinline__ void qkv_place(Ctx& c, int m, int r, int pos0, float 
 }
 template <int M>
 __device__ __forceinline__ void gather_qkv(Ctx& c, const u64* buf, int pos0, const KvRegs& kv) {
-  constexpr int GPT = (M * QKV + NT - 1) / NT;
-  int off[GPT];
-  bool val[GPT];
-#pragma unroll
-  for (int u = 0; u < GPT; ++u) {
-    off[u] = c.tid + u * NT;
-    val[u] = off[u] < M * QKV;
-  }
-#if DF_PAIR16
   constexpr int NP = M * QKV / 2, GPP = (NP + NT - 1) / NT;  // granule pairs; thread t: pairs t, t + NT
   int poff[GPP];
 #pragma unroll
   for (int u = 0; u < GPP; ++u) poff[u] = 2 * min(c.tid + u * NT, NP - 1);  // (a clamped pair is re-read, unused)
-  poll_pairs<GPP, DF_DELAY_E1, DF_REPOLL>(buf, 0x7fffffff, poff, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); },
-                                          [&](const u32x4_t (&g)[GPP]) {
+  poll_pairs<GPP, DELAY_E1, REPOLL>(buf, 0x7fffffff, poff, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); },
+                                    [&](const u32x4_t (&g)[GPP]) {
 #pragma unroll
     for (int u = 0; u < GPP; ++u)
       if (c.tid + u * NT < NP) {
@@ -627,35 +502,20 @@ __device__ __forceinline__ void gather_qkv(Ctx& c, const u64* buf, int pos0, con
       }
   });
   c.stamp();
-  (void)off; (void)val;
-#else
-  poll<GPT, DF_DELAY_E1>(c, buf, off, val, [&](const u64 (&g)[GPT]) {
-#pragma unroll
-    for (int u = 0; u < GPT; ++u)
-      if (val[u]) qkv_place(c, off[u] / QKV, off[u] % QKV, pos0, __uint_as_float((unsigned)g[u]));
-  });
-#endif
   kv_store(c, pos0, kv);
   __syncthreads();
 }
 
 // Attention of rows m < M (positions pos0 + m) over keys 0..pos0+m, all in c.L.Ks / Vs (kv_store +
-// kv_append).  Every WG computes all heads (wave = head), as attn_short_head: lane = (key kj =
+// qkv_place).  Every WG computes all heads (wave = head), as attn_short_head: lane = (key kj =
 // lane & 31, half hh of the head dims), scores from two half dots added by one shuffle,
 // max-subtracted softmax, P.V in key order with the V rows read 8 keys at a time (all in flight
-// together; rows past the last key are read but not used).  The new K/V rows go to the cache,
+// together; rows past the last key are read but not used): one 16-B V read per key over key halves
+// (lane >> 5), the halves' sums exchanged once -- the loop is issue-bound, and 4-B or 8-B reads per
+// key cost 56 us per frame more (profiles/r03_ab_pairs.txt).  The new K/V rows go to the cache,
 // spread over the workgroups, for later steps.
-// DF_PV: the P.V loop's V reads -- 0: two 4-B reads per key (dims lane, lane + 64); 1: one 8-B read
-// (dims 2 lane, +1); 2: one 16-B read per key over key halves (lane >> 5), the halves' sums exchanged
-#ifndef DF_PV
-#define DF_PV 2
-#endif
-#ifndef DF_ATTN_SUB
-#define DF_ATTN_SUB 0  // lab: 1 / 2 move the attention-end mark after the softmax / after P.V (tools/df_stamps.py)
-#endif
 template <int M, bool Q4 = false>
 __device__ __forceinline__ void phase_attn(Ctx& c, int pos0, int layer) {
-  static_assert(!Q4 || DF_PV == 2, "the int4 kernel stages the attention output from the DF_PV 2 loop");
   const int h = c.wave, g = h / (HQ / HKV);
   const float scale = 0.08838834764831845f;  // 1 / sqrt(128)
   const int kj = c.lane & 31, hh = c.lane >> 5;
@@ -687,29 +547,6 @@ __device__ __forceinline__ void phase_attn(Ctx& c, int pos0, int layer) {
     const float pj = kj < n ? expf(s - mx) : 0.f;
     const float l_run = wave_sum(hh == 0 ? pj : 0.f);
     const int pji = __float_as_int(pj);
-    if (DF_ATTN_SUB == 1 && m == M - 1) c.mark();  // lab: the attention mark after the softmax
-#if DF_PV == 1
-    // lane = dims 2 lane, 2 lane + 1 (one 8-B V read per key), keys in order
-    float o0 = 0.f, o1 = 0.f;
-#pragma unroll
-    for (int j0 = 0; j0 < 32; j0 += 8) {
-      if (j0 < n) {
-        float2 vv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) vv[u] = *reinterpret_cast<const float2*>(&c.L.Vs[g][j0 + u][2 * c.lane]);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          if (j0 + u < n) {
-            const float pb = __int_as_float(__builtin_amdgcn_readlane(pji, j0 + u));
-            o0 = fmaf(pb, vv[u].x, o0);
-            o1 = fmaf(pb, vv[u].y, o1);
-          }
-        }
-      }
-    }
-    const float inv = 1.f / l_run;
-    *reinterpret_cast<float2*>(&c.L.att[m][h * HD + 2 * c.lane]) = make_float2(o0 * inv, o1 * inv);
-#elif DF_PV == 2
     // lane = (key half kv = lane >> 5: keys 16 kv + u, dims 4 (lane & 31) .. +3): one 16-B V read per
     // key, the halves' sums added (keys 0-15 first) by one exchange
     const int kv = c.lane >> 5, dq = c.lane & 31;
@@ -755,33 +592,7 @@ __device__ __forceinline__ void phase_attn(Ctx& c, int pos0, int layer) {
       *reinterpret_cast<float4*>(&c.L.att[m][h * HD + 4 * dq]) =
           make_float4((o.x + t.x) * inv, (o.y + t.y) * inv, (o.z + t.z) * inv, (o.w + t.w) * inv);
     }
-#else
-    float o0 = 0.f, o1 = 0.f;
-#pragma unroll
-    for (int j0 = 0; j0 < 32; j0 += 8) {
-      if (j0 < n) {
-        float va[8], vb[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          va[u] = c.L.Vs[g][j0 + u][c.lane];
-          vb[u] = c.L.Vs[g][j0 + u][c.lane + 64];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          if (j0 + u < n) {
-            const float pb = __int_as_float(__builtin_amdgcn_readlane(pji, j0 + u));
-            o0 = fmaf(pb, va[u], o0);
-            o1 = fmaf(pb, vb[u], o1);
-          }
-        }
-      }
-    }
-    const float inv = 1.f / l_run;
-    c.L.att[m][h * HD + c.lane] = o0 * inv;
-    c.L.att[m][h * HD + c.lane + 64] = o1 * inv;
-#endif
   }
-  if (DF_ATTN_SUB == 2) c.mark();  // lab: the attention mark after P.V (before the K/V store + barrier)
   // the new K / V rows -> cache, spread over the workgroups (WG w stores element w of each row:
   // 2 heads x 128 = 256 elements), write-through; the storing threads drain them (vmcnt(0)) before
   // this WG's next publish (phase_mlp), so a reader that saw that hand-off reads them coherently
@@ -842,7 +653,7 @@ __device__ __forceinline__ void phase_mlp(Ctx& c, const WGu& G, const WDn& Wd) {
   if (c.tid < MAXM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this layer's K/V cache stores
   __syncthreads();
   u64* g = c.buf(G_PART, (size_t)NWG * MAXM * D) + (size_t)c.w * MAXM * D;
-  float a[2][2];  // [row 2t + s | t + 512 s][utterance row m]
+  float a[2][2];  // [row 2t + s][utterance row m]
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     a[s][0] = 0.f;
@@ -853,20 +664,12 @@ __device__ __forceinline__ void phase_mlp(Ctx& c, const WGu& G, const WDn& Wd) {
       dotm<M>(Wd.a[s][q][1], c.L.hb[0] + 16 * q + 8, c.L.hb[1] + 16 * q + 8, a[s][0], a[s][1]);
     }
   }
-  if (DF_E4_16) {
-    const unsigned tg = c.tag();
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(g, 0, 0x7fffffff, 0x00020000);
+  const unsigned tg = c.tag();
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(g, 0, 0x7fffffff, 0x00020000);
 #pragma unroll
-    for (int m = 0; m < M; ++m) {
-      const u32x4_t v = {__float_as_uint(a[0][m]), tg, __float_as_uint(a[1][m]), tg};
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs, (m * D + 2 * c.tid) * 8, 0, 16);  // sc1
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      gput(g + c.tid + 512 * s, a[s][0], c.tag());
-      if (M > 1) gput(g + D + c.tid + 512 * s, a[s][1], c.tag());
-    }
+  for (int m = 0; m < M; ++m) {
+    const u32x4_t v = {__float_as_uint(a[0][m]), tg, __float_as_uint(a[1][m]), tg};
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs, (m * D + 2 * c.tid) * 8, 0, 16);  // sc1
   }
 }
 
@@ -875,21 +678,19 @@ template <int M>
 __device__ __forceinline__ void phase_reduce(Ctx& c) {
   const u64* g = c.buf(G_PART, (size_t)NWG * MAXM * D);
   const int v = c.tid >> 1, half = c.tid & 1;
+  // thread (producer v, half): granules off[2m], off[2m + 1] = rows 4w + 2 half, + 1 of v's partials, one
+  // pair.  (Both offsets stay spelled out: computing the even one alone is the same arithmetic, but the
+  // compiler then allocates the kernel's registers differently, and this file's code object is pinned.)
   int off[2 * M];
-  bool val[2 * M];
 #pragma unroll
   for (int m = 0; m < M; ++m)
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      off[2 * m + u] = (v * MAXM + m) * D + 4 * c.w + 2 * half + u;
-      val[2 * m + u] = true;
-    }
-#if DF_PAIR16
+    for (int u = 0; u < 2; ++u) off[2 * m + u] = (v * MAXM + m) * D + 4 * c.w + 2 * half + u;
   int poff[M];
 #pragma unroll
   for (int m = 0; m < M; ++m) poff[m] = off[2 * m];
-  poll_pairs<M, DF_DELAY_E4, DF_REPOLL>(g, 0x7fffffff, poff, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); },
-                                        [&](const u32x4_t (&q)[M]) {
+  poll_pairs<M, DELAY_E4, REPOLL>(g, 0x7fffffff, poff, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); },
+                                  [&](const u32x4_t (&q)[M]) {
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       c.L.red[4 * m + 2 * half][v] = __uint_as_float(q[m].x);
@@ -897,15 +698,6 @@ __device__ __forceinline__ void phase_reduce(Ctx& c) {
     }
   });
   c.stamp();
-  (void)val;
-#else
-  poll<2 * M, DF_DELAY_E4>(c, g, off, val, [&](const u64 (&q)[2 * M]) {
-#pragma unroll
-    for (int m = 0; m < M; ++m)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) c.L.red[4 * m + 2 * half + u][v] = __uint_as_float((unsigned)q[2 * m + u]);
-  });
-#endif
   __syncthreads();
   ++c.e;  // the x hand-off that follows
   if (c.wave < 4 * M) {
@@ -937,7 +729,7 @@ __device__ __forceinline__ void phase_o4(Ctx& c, const WO4& W) {
   }
 }
 // gate/up (load i of wave v: the SiLU*up column 4v + i from its two lane halves) and the down partials
-// of rows 2t, 2t + 1 over the WG's 32 columns -> E4 (two granules per 16-B sc1 store, as DF_E4_16)
+// of rows 2t, 2t + 1 over the WG's 32 columns -> E4 (two granules per 16-B sc1 store, as phase_mlp)
 template <int M, bool SC>
 __device__ __forceinline__ void phase_mlp4(Ctx& c, const WGu4& G, const WDn4& Wd) {
 #pragma unroll
@@ -974,8 +766,8 @@ __device__ __forceinline__ void gather_x4(Ctx& c, const u64* buf, float2 nw) {
 #pragma unroll
   for (int m = 0; m < M; ++m) poff[m] = m * D + 2 * c.tid;
   float sq[MAXM], pr[MAXM];
-  poll_pairs<M, DELAY, DF_REPOLL>(buf, 0x7fffffff, poff, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); },
-                                  [&](const u32x4_t (&g)[M]) {
+  poll_pairs<M, DELAY, REPOLL>(buf, 0x7fffffff, poff, c.tag(), [&](unsigned spin) { return spin_fail(c, spin); },
+                               [&](const u32x4_t (&g)[M]) {
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       const float v0 = __uint_as_float(g[m].x), v1 = __uint_as_float(g[m].z);
@@ -1118,31 +910,21 @@ __device__ __forceinline__ void head_publish(Ctx& c, float s, float t, int n_val
   __syncthreads();
 }
 
-// Gather the 256 arg-max keys -> code (every WG identical).  Thread t polls granule t (word t & 1 of
-// key t / 2); the two words meet by one lane swap, every wave takes the max of its 32 keys, and one
-// barrier joins the 8 wave maxima -- the max of exact keys, so the order is immaterial.
+// Gather the 256 arg-max keys -> code (every WG identical).  Key t is granule pair t (its two words):
+// threads t < NWG poll one pair each (the others hold key 0), every wave takes the max of its keys,
+// and one barrier joins the 8 wave maxima -- the max of exact keys, so the order is immaterial.
 __device__ __forceinline__ int gather_code(Ctx& c, int V) {
-  static_assert(NWG * 2 == NT, "one key word per thread");
-#if DF_PAIR16
-  // key t = granule pair t: threads t < NWG poll one pair each (the others hold key 0)
+  static_assert(NWG <= NT, "one key per thread");
   unsigned long long b = 0ull;
   if (c.tid < NWG) {
     const int poff[1] = {2 * c.tid};
-    poll_pairs<1, DF_DELAY_E6, DF_REPOLL>(c.rbuf(G_ARG, NWG * 2), 0x7fffffff, poff, c.tag(),
-                                          [&](unsigned spin) { return spin_fail(c, spin); },
-                                          [&](const u32x4_t (&g)[1]) { b = ((unsigned long long)g[0].x << 32) | g[0].z; });
+    poll_pairs<1, DELAY_E6, REPOLL>(c.rbuf(G_ARG, NWG * 2), 0x7fffffff, poff, c.tag(),
+                                    [&](unsigned spin) { return spin_fail(c, spin); },
+                                    [&](const u32x4_t (&g)[1]) { b = ((unsigned long long)g[0].x << 32) | g[0].z; });
   }
   c.stamp();
-#else
-  const int off[1] = {c.tid};
-  const bool val[1] = {true};
-  unsigned wv = 0;
-  poll<1, DF_DELAY_E6>(c, c.rbuf(G_ARG, NWG * 2), off, val, [&](const u64 (&g)[1]) { wv = (unsigned)g[0]; });
-  const unsigned ov = __shfl_xor(wv, 1, 64);
-  unsigned long long b = (c.tid & 1) ? (((unsigned long long)ov << 32) | wv) : (((unsigned long long)wv << 32) | ov);
-#endif
 #pragma unroll
-  for (int o = 32; o > (DF_PAIR16 ? 0 : 1); o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {
     const unsigned long long t = __shfl_xor(b, o, 64);
     b = t > b ? t : b;
   }
@@ -1268,7 +1050,7 @@ __device__ __forceinline__ int gumbel_code(Ctx& c, int V) {
     val[u] = off[u] < NG;
   }
   unsigned* words = reinterpret_cast<unsigned*>(&c.L.red[0][0]);
-  poll<GPT, DF_DELAY_E6>(c, c.rbuf(G_GUM, NWG * 3), off, val, [&](const u64 (&g)[GPT]) {
+  poll<GPT, DELAY_E6>(c, c.rbuf(G_GUM, NWG * 3), off, val, [&](const u64 (&g)[GPT]) {
 #pragma unroll
     for (int u = 0; u < GPT; ++u)
       if (val[u]) words[off[u]] = (unsigned)g[u];
@@ -1324,11 +1106,9 @@ struct Pre4 {  // the int4 kernel's (the ci heads stay bf16: audio_head is not q
   float2 nw1;
 };
 template <bool Q4> using PreT = std::conditional_t<Q4, Pre4, Pre>;
-#ifndef DF_GU4_EARLY
-#define DF_GU4_EARLY 2  // int4: gate/up loads per wave fetched before the attention (of 4; the rest after o_proj)
-#endif
-static_assert(DF_FOLD && DF_PAIR16 && DF_E4_16 && DF_KVDIRECT && DF_TAB16 && DF_GU_E45 == 0 && !DF_DN_EARLY &&
-              !DF_DN_AFTER_E1, "the int4 kernel implements the default variants only");
+// int4: gate/up loads per wave (of 4) fetched before the attention, the rest after o_proj -- the
+// same half / half split as GU_EARLY
+constexpr int GU4_EARLY = 2;
 // weight-format dispatch of the loaders / phases the layer calls
 template <bool Q4, typename P> __device__ __forceinline__ void ld_dn(Ctx& c, int l, P& r) {
   if constexpr (Q4) load_dn4(c, l, r.wd); else load_dn(c, l, r.wd);
@@ -1341,7 +1121,7 @@ template <bool Q4, typename P> __device__ __forceinline__ void ld_o(Ctx& c, int 
 }
 template <bool Q4, bool EARLY, typename P> __device__ __forceinline__ void ld_gu(Ctx& c, int l, P& r) {
   if constexpr (Q4) {
-    if constexpr (EARLY) load_gu4<0, DF_GU4_EARLY>(c, l, r.wg); else load_gu4<DF_GU4_EARLY, 4>(c, l, r.wg);
+    if constexpr (EARLY) load_gu4<0, GU4_EARLY>(c, l, r.wg); else load_gu4<GU4_EARLY, 4>(c, l, r.wg);
   } else {
     if constexpr (EARLY) load_gu<0, GU_EARLY>(c, l, r.wg); else load_gu<GU_EARLY, 8>(c, l, r.wg);
   }
@@ -1366,9 +1146,8 @@ __device__ __forceinline__ void decoder_layer(Ctx& c, int l, int step, int pos0,
     // loads are in flight together, ahead of the down prefetch (vmcnt retires in issue order)
     const float* t = p.qkv0_tab + ((size_t)(step - 1) * p.V + c.code) * QKV;
     const float* xr = p.proj_tab + ((size_t)(step - 1) * p.V + c.code) * D;
-#if DF_TAB16
-    // DF_TAB16: the two rows as 16-B loads (640 float4: q|k|v 0..383, x 384..639; thread t takes
-    // float4 t and, t < 128, float4 512 + t), one round trip, fewer load instructions
+    // the two rows as 16-B loads (640 float4: q|k|v 0..383, x 384..639; thread t takes float4 t and,
+    // t < 128, float4 512 + t), one round trip, fewer load instructions
     constexpr int NQ4 = QKV / 4, NX4 = D / 4;
     const float4* t4 = reinterpret_cast<const float4*>(t);
     const float4* x4 = reinterpret_cast<const float4*>(xr);
@@ -1388,28 +1167,8 @@ __device__ __forceinline__ void decoder_layer(Ctx& c, int l, int step, int pos0,
     };
     put4(i0, va);
     if (i1 < NQ4 + NX4) put4(i1, vb);
-#else
-    float tv[(QKV + NT - 1) / NT], xv[D / NT];
-#pragma unroll
-    for (int j = 0; j < (QKV + NT - 1) / NT; ++j) tv[j] = c.tid + j * NT < QKV ? t[c.tid + j * NT] : 0.f;
-#pragma unroll
-    for (int j = 0; j < D / NT; ++j) xv[j] = xr[c.tid + j * NT];
-    load_dn(c, l, r.wd);
-#pragma unroll
-    for (int j = 0; j < (QKV + NT - 1) / NT; ++j)
-      if (c.tid + j * NT < QKV) {
-        if (DF_KVDIRECT) qkv_place(c, 0, c.tid + j * NT, pos0, tv[j]);
-        else L.qkv[0][c.tid + j * NT] = tv[j];
-      }
-#pragma unroll
-    for (int j = 0; j < D / NT; ++j) L.x[0][c.tid + j * NT] = xv[j];
-#endif
     if (c.tid < M * (HD / 2)) L.rope[c.tid / (HD / 2)][c.tid % (HD / 2)] = rp;
-    __syncthreads();  // L.qkv complete before kv_append reads it
-    if (!DF_KVDIRECT) {
-      kv_append<M>(c, pos0);
-      __syncthreads();
-    }
+    __syncthreads();  // q, the new K / V rows and x complete before the attention reads them
   } else {
     KvRegs kv;
     if (FIRST && c.tid < M * (HD / 2)) L.rope[c.tid / (HD / 2)][c.tid % (HD / 2)] = rp;
@@ -1418,59 +1177,35 @@ __device__ __forceinline__ void decoder_layer(Ctx& c, int l, int step, int pos0,
       if (FIRST) rms_rows4<M>(c, r.nw1);               // (its barriers also publish the RoPE rows)
       phase_qkv4<M, !FIRST>(c, pos0, r.wq);            // -> E1
     } else {
-      if (FIRST || !DF_FOLD) rms_rows<M>(c, r.nw1);  // (its barriers also publish the RoPE rows)
-      phase_qkv<M, DF_FOLD && !FIRST>(c, pos0, r.wq);   // -> E1
+      if (FIRST) rms_rows<M>(c, r.nw1);                // (its barriers also publish the RoPE rows)
+      phase_qkv<M, !FIRST>(c, pos0, r.wq);             // -> E1
     }
     // prefetches issued after the publish (its RoPE operand load would otherwise retire behind
-    // them in vmcnt order), still ahead of the hand-off wait they hide under
+    // them in vmcnt order), still ahead of the hand-off wait they hide under.  The next layer's down
+    // or gate/up slices are NOT fetched in the previous E4 / E5 window: those polls then queue behind
+    // them, +80-150 us per frame (DESIGN.md, round 3 "tried, not kept").
     kv_issue(c, l, pos0, kv);
-    if ((FIRST || !DF_DN_EARLY) && !DF_DN_AFTER_E1) ld_dn<Q4>(c, l, r);
-#if DF_KVDIRECT
+    ld_dn<Q4>(c, l, r);
     gather_qkv<M>(c, c.rbuf(G_QKV, MAXM * QKV), pos0, kv);  // (its barrier publishes the history too)
     ++c.e;
-#else
-    gather<(M * QKV + NT - 1) / NT>(c, c.rbuf(G_QKV, MAXM * QKV), M * QKV, &L.qkv[0][0]);
-    ++c.e;
-    kv_store(c, pos0, kv);
-    kv_append<M>(c, pos0);
-    __syncthreads();
-#endif
   }
   c.refresh();
   c.mark();
   const float2 nw2 = nw_fetch(c, p.n2[l]);
-  // DF_DN_AFTER_E1: the down slices issued after the q|k|v wait (not ahead of it) on layers that wait
-  if constexpr (!Q4) {
-    if (DF_DN_AFTER_E1 && !(FIRST && step > 1)) load_dn(c, l, r.wd);
-    if (FIRST || DF_GU_E45 == 0) load_gu<0, GU_EARLY>(c, l, r.wg);  // (layers >= 1: rows < DF_GU_E45 came at E4 / E5)
-    else if (DF_GU_E45 < GU_EARLY) load_gu<DF_GU_E45, GU_EARLY>(c, l, r.wg);
-  } else {
-    ld_gu<Q4, true>(c, l, r);
-  }
+  ld_gu<Q4, true>(c, l, r);
   phase_attn<M, Q4>(c, pos0, l);
-  if (DF_ATTN_SUB == 0) c.mark();
+  c.mark();
   if constexpr (Q4) phase_o4<M>(c, r.wo);             // -> E3
   else phase_o<M>(c, r.wo);
   c.mark();
   ld_gu<Q4, false>(c, l, r);
   if (!LAST) { ld_qkv<Q4>(c, l + 1, r); ld_o<Q4>(c, l + 1, r); }
-#if DF_FOLD
-  if constexpr (Q4) gather_x4<M, DF_DELAY_E3>(c, c.rbuf(G_X, MAXM * D), nw2);  // E3 -> x, xq = x * n2
-  else gather_x<M, DF_DELAY_E3>(c, c.rbuf(G_X, MAXM * D), nw2);  // E3 -> x, xn = x * n2
-#else
-  gather<M * D / NT>(c, c.rbuf(G_X, MAXM * D), M * D, &L.x[0][0]);
-#endif
+  if constexpr (Q4) gather_x4<M, DELAY_E3>(c, c.rbuf(G_X, MAXM * D), nw2);  // E3 -> x, xq = x * n2
+  else gather_x<M, DELAY_E3>(c, c.rbuf(G_X, MAXM * D), nw2);  // E3 -> x, xn = x * n2
   ++c.e;
   c.refresh();
-  if (!DF_FOLD) rms_rows<M>(c, nw2);
   if constexpr (Q4) phase_mlp4<M, true>(c, r.wg, r.wd);  // -> E4
-  else phase_mlp<M, DF_FOLD>(c, r.wg, r.wd);                // -> E4
-  // DF_DN_EARLY: the next layer's down slices stream during this layer's E4 / E5 (its registers
-  // were just consumed) instead of during the next E1 wait
-  if constexpr (!Q4) {
-    if (DF_DN_EARLY && !LAST) load_dn(c, l + 1, r.wd);
-    if (DF_GU_E45 > 0 && !LAST) load_gu<0, DF_GU_E45>(c, l + 1, r.wg);
-  }
+  else phase_mlp<M, true>(c, r.wg, r.wd);                // -> E4
   r.nw1 = nw_fetch(c, LAST ? p.norm : p.n1[l + 1]);  // next layer's norm, or the final one
   c.mark();
   if (LAST) {
@@ -1482,12 +1217,8 @@ __device__ __forceinline__ void decoder_layer(Ctx& c, int l, int step, int pos0,
   }
   c.refresh();
   phase_reduce<M>(c);                                 // waits E4, -> E5
-#if DF_FOLD
-  if constexpr (Q4) gather_x4<M, DF_DELAY_E5>(c, c.rbuf(G_X, MAXM * D), r.nw1);  // E5 -> x, xq
-  else gather_x<M, DF_DELAY_E5>(c, c.rbuf(G_X, MAXM * D), r.nw1);  // E5 -> x, xn = x * (next n1 | final norm)
-#else
-  gather<M * D / NT>(c, c.rbuf(G_X, MAXM * D), M * D, &L.x[0][0]);
-#endif
+  if constexpr (Q4) gather_x4<M, DELAY_E5>(c, c.rbuf(G_X, MAXM * D), r.nw1);  // E5 -> x, xq
+  else gather_x<M, DELAY_E5>(c, c.rbuf(G_X, MAXM * D), r.nw1);  // E5 -> x, xn = x * (next n1 | final norm)
   ++c.e;
 }
 
@@ -1501,13 +1232,8 @@ __device__ __forceinline__ void run_step(Ctx& c, int step, PreT<Q4>& r) {
   decoder_layer<M, false, true, Q4>(c, NL - 1, step, pos0, r);
   // ci head on the last row: final norm, audio_head[step - 1] (generation.py:79)
   c.refresh();
-#if DF_FOLD
   phase_head<D, Q4>(c, p.audio_head + (size_t)(step - 1) * p.VP * D, p.V, r.wh.a, r.wh.x, p.ci_logits + (size_t)(step - 1) * p.VP,
                     step, M - 1, row_rs(c, M - 1));  // -> E6
-#else
-  rms_rows<1>(c, r.nw1, M - 1);
-  phase_head<D>(c, p.audio_head + (size_t)(step - 1) * p.VP * D, p.V, r.wh.a, r.wh.x, p.ci_logits + (size_t)(step - 1) * p.VP, step);  // -> E6
-#endif
   KvRegs kv0;  // layer 0's cached K/V rows of the next step: in flight during the head's hand-off,
   if (step + 1 < p.K) kv_issue(c, 0, step + 1, kv0);
   const int ci = head_code(c, p.V, step);

@@ -77,25 +77,15 @@ enum { CW_F1 = 0, CW_F2 = CW_F1 + 2 * NQT, CW_F3 = CW_F2 + RMAX, CW_FH = CW_F3 +
        CW_F5 = CW_C4 + NDT, CW_FS = CW_F5 + NDT, CW_N = CW_FS + 128 };  // FS: head (tile, row tile)s done (sampled steps)
 // int4 (two row tiles): the second row tile's QKV and o_proj workgroups
 constexpr int Q1_WG0 = A_WG0 + 64, O1_WG0 = Q1_WG0 + NQT;
-// XSD_QSPLIT (bf16): each QKV tile's K split over two workgroups (stages 0-7 on w < 48, 8-15 on QB_WG0 +
-// the tile: workgroups idle until gate/up), one K stage per wave; they publish raw partial sums and the
-// attention adds the halves, applies the row scale and RoPE and appends its row's K / V.  0: one
-// workgroup per tile (A/B).
-#ifndef XSD_QSPLIT
-#define XSD_QSPLIT 1
-#endif
+// bf16: each QKV tile's K is split over two workgroups (stages 0-7 on w < 48, 8-15 on QB_WG0 + the
+// tile: workgroups idle until gate/up), one K stage per wave; they publish raw partial sums and the
+// attention adds the halves, applies the row scale and RoPE and appends its row's K / V
+// (profiles/r06_ab_xsd_qsplit.txt).
 constexpr int QB_WG0 = NWG - NQT;
 constexpr int CW_STRIDE = 32;
 
-#ifndef XSD_UNION
-#define XSD_UNION 1  // lab: 0 keeps the attention buffers apart from the MFMA reduction slots
-#endif
 struct Lds {
-#if XSD_UNION
   union {
-#else
-  struct {
-#endif
     float red[NWV][2][16][64];  // MFMA roles: the per-wave accumulators of up to two tiles
     struct {                    // attention workgroups (wave = query head): cached keys / values 0..pos-1 of
       float Ks[HKV][32][HD + 4];//   both kv heads (rows padded: conflict-free row-parallel reads), each
@@ -128,13 +118,7 @@ struct Ctx {
   }
 };
 
-__device__ __forceinline__ bool spin_fail(const Ctx& c, unsigned spin) {
-  if (spin >= SPIN_LIMIT || ((spin & 255) == 255 && __hip_atomic_load(c.p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-    __hip_atomic_store(c.p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-  }
-  return false;
-}
+__device__ __forceinline__ bool spin_fail(const Ctx& c, unsigned spin) { return handoff::spin_fail(c.p.err, SPIN_LIMIT, spin); }
 __device__ __forceinline__ unsigned ld_cw(const unsigned* a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // lanes < n of wave 0 wait until word idx(lane) has reached `target` (flags hold tags, tickets counts:
 // both only grow), then the workgroup barrier
@@ -388,7 +372,7 @@ __device__ __forceinline__ void role_q(Ctx& c, int l, int T, const WTile<Q4>& W)
   c.mark(2);
 }
 
-// bf16 XSD_QSPLIT: QKV tile T over K half HALF (stages 8 HALF .. 8 HALF + 7, one per wave) -> the raw
+// bf16: QKV tile T over K half HALF (stages 8 HALF .. 8 HALF + 7, one per wave) -> the raw
 // partial sums qkvp[HALF][m][n] (role_a adds the halves, scales, rotates); the half-0 workgroups also
 // publish the row scales (row_scales / row_scale, their loads under the operand loads) in qkvr[T][m]
 template <int HALF>
@@ -481,8 +465,8 @@ __device__ __forceinline__ void role_a(Ctx& c, int l) {
         __hip_atomic_store(p.code_buf + m, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     } else {
-      // q tiles 4h..4h+3, k tiles 32 + 4g.., v tiles 40 + 4g.. (XSD_QSPLIT: of both K halves)
-      constexpr bool QS = !Q4 && XSD_QSPLIT;
+      // q tiles 4h..4h+3, k tiles 32 + 4g.., v tiles 40 + 4g.. (bf16: of both K halves)
+      constexpr bool QS = !Q4;
       if (lane < (QS ? 24 : 12)) {
         const int lt = lane % 12;
         const int t = lt < 4 ? 4 * h + lt : (lt < 8 ? HQ * 4 + 4 * g + lt - 4 : (HQ + HKV) * 4 + 4 * g + lt - 8);
@@ -890,7 +874,7 @@ __device__ __forceinline__ void run_layers(Ctx& c) {
   constexpr int MT = Q4 ? 2 : 1;
   constexpr bool IS_Q = CLS == C_Q || CLS == C_Q1 || CLS == C_QB, IS_O = CLS == C_O || CLS == C_O1;
   constexpr int RT0 = (CLS == C_Q1 || CLS == C_O1) ? 1 : 0, RT1 = Q4 ? RT0 + 1 : MT;
-  constexpr bool QS = !Q4 && XSD_QSPLIT;  // bf16 QKV K halves: stage 8 HALF + wave
+  constexpr bool QS = !Q4;  // bf16 QKV K halves: stage 8 HALF + wave
   constexpr int QHALF = CLS == C_QB ? 1 : 0, QNS = QS ? 1 : 2;
   const int qst = QS ? 8 * QHALF + c.wave : 2 * c.wave;
   const int qt = c.w - (CLS == C_Q1 ? Q1_WG0 : (CLS == C_QB ? QB_WG0 : 0)), ot = c.w - (CLS == C_O1 ? O1_WG0 : O_WG0);
@@ -979,7 +963,7 @@ __device__ __forceinline__ void step_kernel(const DecStepXsArgs& p) {
     else if (c.w < O1_WG0 + NDT) run_layers<Q4, C_O1>(c);
     else run_layers<Q4, C_P>(c);
   } else if (p.head_w && c.w < H_WG0 + p.head_tiles) run_layers<Q4, C_H>(c);
-  else if (XSD_QSPLIT && c.w >= QB_WG0) run_layers<Q4, C_QB>(c);
+  else if (c.w >= QB_WG0) run_layers<Q4, C_QB>(c);
   else run_layers<Q4, C_P>(c);
   if (p.sample && c.w < p.M) role_s(c);
   if (p.stamps && c.tid == 0) p.stamps[(size_t)c.w * DEC_XSD_STAMPS + DEC_XSD_STAMPS - 1] = __builtin_amdgcn_s_memrealtime();

@@ -147,11 +147,6 @@ extern "C" int csm_gemm_stamps(unsigned long long* out, int n) {
 #define GSTAMP(i) do {} while (0)
 #endif
 
-#ifndef GW_LAB
-#define GW_LAB 0  // lab ablations (tools/variant.sh -DGW_LAB=bits, results invalid): 1 staging without norm / split /
-                  // group sums, 2 no int4 scale / bias fold, 4 no MFMA (operands consumed by one VALU op), 8 no int4
-                  // -> bf16 expansion, 16 no LDS reads of the activation fragments
-#endif
 template <bool Q4, int MT, int NBR, int PD, bool NT, int NW = 4>
 __global__ __launch_bounds__(64 * NW) void gemm_wide_kernel(GemvParams p) {
   constexpr int NB = MT * 32, NTH = 64 * NW;
@@ -167,15 +162,11 @@ __global__ __launch_bounds__(64 * NW) void gemm_wide_kernel(GemvParams p) {
   constexpr int CT_BYTES = NB * (NBR + 1) * 4;
   constexpr int SM = XS_BYTES > CT_BYTES ? XS_BYTES : CT_BYTES;
   __shared__ __attribute__((aligned(16))) unsigned char smem[SM];
-  // GW_QB: the int4 bias term sum_g bias_g[n] X_g[m] on the matrix cores, 16 stages at a time (X_g split in
+  // int4: the bias term sum_g bias_g[n] X_g[m] runs on the matrix cores, 16 stages at a time (X_g split in
   // three exact bf16 parts, the bf16 biases as the B operand: three MFMAs per tile pair) instead of an fmaf per
-  // accumulator per stage; X_g and the biases wait in 32-stage rings
-#ifndef GW_QB
-#define GW_QB 1
-#endif
-  constexpr bool QB = Q4 && GW_QB != 0;
-  __shared__ __attribute__((aligned(16))) float xsum[QB ? 32 : 2][NB];  // int4: the stage's sum of x per batch row
-  __shared__ uint16_t bsh[QB ? 32 : 1][QB ? NBR : 1];
+  // accumulator per stage (profiles/r05_ab_q4_bias_mfma.txt); X_g and the biases wait in 32-stage rings
+  __shared__ __attribute__((aligned(16))) float xsum[Q4 ? 32 : 2][NB];  // int4: the stage's sum of x per batch row
+  __shared__ uint16_t bsh[Q4 ? 32 : 1][Q4 ? NBR : 1];
   __shared__ float ssb[NB];
   __shared__ int last;
   auto Xs = [&](int buf, int part, int t, int s) {
@@ -250,20 +241,11 @@ __global__ __launch_bounds__(64 * NW) void gemm_wide_kernel(GemvParams p) {
     }
   };
   auto store = [&](const Stage& g, int buf, bool live, int st) {
-    const int xslot = QB ? (st & 31) : buf;
+    const int xslot = Q4 ? (st & 31) : buf;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int c = x_c + RPT * i;
       float v[4] = {g.xr[i].x, g.xr[i].y, g.xr[i].z, g.xr[i].w};
-      if constexpr ((GW_LAB & 1) != 0) {  // the same LDS stores of raw bits: the staging's memory side only
-        const u32x2_t raw = {__float_as_uint(v[0]) ^ __float_as_uint(g.nwr.x), __float_as_uint(v[2])};
-        const int sl = (c & 31) + 33 * st_h;
-        *(reinterpret_cast<u32x2_t*>(&Xs(buf, 0, c >> 5, st_s)[sl]) + st_j) = raw;
-        *(reinterpret_cast<u32x2_t*>(&Xs(buf, 1, c >> 5, st_s)[sl]) + st_j) = raw;
-        *(reinterpret_cast<u32x2_t*>(&Xs(buf, 2, c >> 5, st_s)[sl]) + st_j) = raw;
-        if (live && (tid & 15) == 0) xsum[xslot][c] = v[1];
-        continue;
-      }
       if (norm) {
         const float nw4[4] = {g.nwr.x, g.nwr.y, g.nwr.z, g.nwr.w};
 #pragma unroll
@@ -316,8 +298,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_wide_kernel(GemvParams p) {
             uint32_t word = g.w[i][0][s];
             if constexpr (KW == 2) word = kh ? g.w[i][0][NS + s] : g.w[i][0][s];
             if constexpr (KW == 4) word = kh == 0 ? g.w[i][0][0] : (kh == 1 ? g.w[i][0][1] : (kh == 2 ? g.w[i][0][2] : g.w[i][0][3]));
-            if constexpr ((GW_LAB & 8) != 0) b[i] = __builtin_bit_cast(bf16x8_t, u32x4_t{word, word ^ 1u, word ^ 2u, word ^ 3u});
-            else b[i] = __builtin_bit_cast(bf16x8_t, xs::q4_word_bf16(word));
+            b[i] = __builtin_bit_cast(bf16x8_t, xs::q4_word_bf16(word));
           } else {
             b[i] = __builtin_bit_cast(bf16x8_t, g.w[i][s]);
           }
@@ -326,17 +307,15 @@ __global__ __launch_bounds__(64 * NW) void gemm_wide_kernel(GemvParams p) {
         for (int t = 0; t < MT; ++t)
 #pragma unroll
           for (int part = 0; part < 3; ++part) {
-            const bf16x8_t a = (GW_LAB & 16) != 0 ? __builtin_bit_cast(bf16x8_t, u32x4_t{(uint32_t)slot, (uint32_t)part, (uint32_t)t, (uint32_t)(step + it)})
-                                                  : __builtin_bit_cast(bf16x8_t, Xs(buf, part, t, step)[slot]);
+            const bf16x8_t a = __builtin_bit_cast(bf16x8_t, Xs(buf, part, t, step)[slot]);
 #pragma unroll
             for (int i = 0; i < RTW; ++i) {
-              if constexpr ((GW_LAB & 4) != 0) gq[t][i][part] += __builtin_bit_cast(float, __builtin_bit_cast(u32x4_t, a).x ^ __builtin_bit_cast(u32x4_t, b[i]).y);
-              else if constexpr (Q4) gq[t][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[i], gq[t][i], 0, 0, 0);
+              if constexpr (Q4) gq[t][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[i], gq[t][i], 0, 0, 0);
               else acc[t][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[i], acc[t][i], 0, 0, 0);
             }
           }
       }
-      if constexpr (QB) {  // acc += scale * S_g; the biases to their ring, their products every 16 stages
+      if constexpr (Q4) {  // acc += scale * S_g; the biases to their ring, their products every 16 stages
         if (kh == 0 && lane < 32)
 #pragma unroll
           for (int i = 0; i < RTW; ++i) bsh[it & 31][32 * (rt0 + i) + lane] = (uint16_t)(g.sb[i] >> 16);
@@ -373,26 +352,6 @@ __global__ __launch_bounds__(64 * NW) void gemm_wide_kernel(GemvParams p) {
 #pragma unroll
               for (int q = 0; q < 3; ++q)
                 acc[t][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, pa[q]), __builtin_bit_cast(bf16x8_t, bw), acc[t][i], 0, 0, 0);
-            }
-          }
-        }
-      } else if constexpr (Q4) {  // acc += scale * S_g + bias * X_g: this lane's weight row, 16 batch rows
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-          float xs[16];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4_t x4 = kh == 0 ? *reinterpret_cast<const f32x4_t*>(&xsum[buf][32 * t + 8 * q + 4 * h]) : f32x4_t{};
-            xs[4 * q] = x4.x; xs[4 * q + 1] = x4.y; xs[4 * q + 2] = x4.z; xs[4 * q + 3] = x4.w;
-          }
-#pragma unroll
-          for (int i = 0; i < RTW; ++i) {
-            const float sc = bf16_lo(g.sb[i]), bi = bf16_hi(g.sb[i]);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-              if constexpr ((GW_LAB & 2) != 0) { acc[t][i][j] += gq[t][i][j]; continue; }
-              acc[t][i][j] = fmaf(sc, gq[t][i][j], acc[t][i][j]);
-              acc[t][i][j] = fmaf(bi, xs[j], acc[t][i][j]);
             }
           }
         }

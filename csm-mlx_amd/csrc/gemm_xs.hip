@@ -114,11 +114,8 @@ __global__ __launch_bounds__(64 * XW) void gemm_xs_kernel(GemvParams p) {
   // [x S/8, (x + 1) S/8), so each operand slice reaches one L2.  Same (tile, slice) work items, same
   // combine order: outputs unchanged.  (At 32 bf16 rows the operand is half the size and the tile-major
   // order, which keeps a tile's slices and its combine inside one XCD, measured faster: r04_ab_xcd_map.)
-#ifndef XS_XCD_Q4
-#define XS_XCD_Q4 1  // lab: 0 keeps the tile-major placement (A/B)
-#endif
   int tile = blockIdx.x, slice = blockIdx.y;
-  if constexpr (Q4 && MT == 2 && XS_XCD_Q4 != 0) {
+  if constexpr (Q4 && MT == 2) {
     const int T = gridDim.x, S = gridDim.y, L = blockIdx.x + T * blockIdx.y;
     if (S % 8 == 0) {
       slice = (L & 7) * (S / 8) + (L >> 3) / T;
@@ -148,27 +145,15 @@ __global__ __launch_bounds__(64 * XW) void gemm_xs_kernel(GemvParams p) {
   struct St {
     u32x4_t w[RTW][Q4 ? 1 : 4];
     uint32_t sb[RTW];
-    u32x4_t a[MT][XS_F32 ? 4 : 3][XS_F32 ? 2 : 4];  // XS_F32: [t][s][half] fp32; else [t][part][s]
+    u32x4_t a[MT][4][2];  // [t][s][half] fp32 (xs.h)
   };
-  // the three bf16 parts of row tile t, step s (XS_F32: split here from the fp32 fragment)
-  auto parts = [&](const St& g, int t, int s, u32x4_t (&pt)[3]) {
-    if constexpr (XS_F32 != 0) {
-      xs::split_frag(g.a[t][s][0], g.a[t][s][1], pt);
-    } else {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) pt[q] = g.a[t][q][s];
-    }
-  };
+  // the three bf16 parts of row tile t, step s, split here from the fp32 fragment
+  auto parts = [&](const St& g, int t, int s, u32x4_t (&pt)[3]) { xs::split_frag(g.a[t][s][0], g.a[t][s][1], pt); };
   // stage j of this wave (j >= wst: zero-sized descriptors, no traffic) -- straight-line loads
   auto load = [&](int j, St& g) {
     const bool live = j < wst;
     const int st = ws0 + (live ? j : 0);
-#ifndef XS_LAB
-#define XS_LAB 0  // lab ablations (tools/variant.sh -DXS_LAB=bits, results invalid): 1 no MFMA, 2 no activation
-                  // traffic, 4 no weight traffic, 8 no split-K exchange / epilogue, 16 stop after the waves'
-                  // reduction
-#endif
-    const __amdgpu_buffer_rsrc_t wr = (live && !(XS_LAB & 4)) ? wrs : zrs, ar = (live && !(XS_LAB & 2)) ? ars : zrs;
+    const __amdgpu_buffer_rsrc_t wr = live ? wrs : zrs, ar = live ? ars : zrs;
 #pragma unroll
     for (int i = 0; i < RTW; ++i) {
       if constexpr (Q4) {
@@ -182,19 +167,11 @@ __global__ __launch_bounds__(64 * XW) void gemm_xs_kernel(GemvParams p) {
     }
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
-      if constexpr (XS_F32 != 0) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
+      for (int s = 0; s < 4; ++s)
 #pragma unroll
-          for (int hf = 0; hf < 2; ++hf)
-            g.a[t][s][hf] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(ar, lane * 16, (((t * nks + st) * 4 + s) * 2 + hf) * 1024, 0));
-      } else {
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-#pragma unroll
-          for (int s = 0; s < 4; ++s)
-            g.a[t][q][s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(ar, lane * 16, ((t * nks + st) * 12 + q * 4 + s) * 1024, 0));
-      }
+        for (int hf = 0; hf < 2; ++hf)
+          g.a[t][s][hf] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(ar, lane * 16, (((t * nks + st) * 4 + s) * 2 + hf) * 1024, 0));
     }
   };
   f32x16_t acc[MT][RTW];
@@ -262,7 +239,7 @@ __global__ __launch_bounds__(64 * XW) void gemm_xs_kernel(GemvParams p) {
 #pragma unroll
               for (int i = 0; i < RTW; ++i)
                 gq[t][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, pt[q]), b[i], gq[t][i], 0, 0, 0);
-            if constexpr (XS_F32 != 0 && MT > 1) __builtin_amdgcn_sched_barrier(0);  // one tile's parts live at a time (no spills)
+            if constexpr (MT > 1) __builtin_amdgcn_sched_barrier(0);  // one tile's parts live at a time (no spills)
           }
         }
         const int jst = j0 + d;
@@ -283,19 +260,6 @@ __global__ __launch_bounds__(64 * XW) void gemm_xs_kernel(GemvParams p) {
               acc[t][i][jj] = fmaf(bi, xr[jj], acc[t][i][jj]);
             }
           }
-        }
-      } else if constexpr ((XS_LAB & 1) != 0) {  // lab: operands consumed by one VALU op each, no MFMA
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          u32x4_t pt[MT][3];
-#pragma unroll
-          for (int t = 0; t < MT; ++t) parts(g[d], t, s, pt[t]);
-#pragma unroll
-          for (int q = 0; q < 3; ++q)
-#pragma unroll
-            for (int t = 0; t < MT; ++t) acc[t][0][s] += __uint_as_float(pt[t][q].x ^ pt[t][q].w);
-#pragma unroll
-          for (int i = 0; i < RTW; ++i) acc[0][i][4 + s] += __uint_as_float(g[d].w[i][s].y ^ g[d].w[i][s].z);
         }
       } else {
 #pragma unroll
@@ -336,17 +300,6 @@ __global__ __launch_bounds__(64 * XW) void gemm_xs_kernel(GemvParams p) {
   __shared__ int last;
   XS_STAMP(2);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the LDS-DMA prefetch too; the barrier below publishes it)
-  if constexpr ((XS_LAB & 8) != 0) {  // lab: the K loop alone (one store keeps it live)
-    float v = 0.f;
-#pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-      for (int i = 0; i < RTW; ++i)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v += acc[t][i][j];
-    if (v == 1.2345f) p.out[tid] = v;
-    return;
-  }
   if constexpr (RED_HALF) {
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
@@ -414,10 +367,6 @@ __global__ __launch_bounds__(64 * XW) void gemm_xs_kernel(GemvParams p) {
   }
   __syncthreads();
   XS_STAMP(3);
-  if constexpr ((XS_LAB & 16) != 0) {  // lab: stop after the waves' reduction (no exchange, no epilogue)
-    if (ct[tid & 31][0] == 1.2345f) p.out[tid] = 0.f;
-    return;
-  }
   if (ks > 1) {
     // slice partial [NB][NBR] write-through, ticket; the last slice to arrive sums all in slice order
     const int slab_f = NB * NBR;
@@ -753,10 +702,7 @@ void launch_gemm_xs(const GemvParams& p0, int epi, hipStream_t st, bool nt_w, in
 #define GX_M(Q_) do { if (p.M > 32) { if (rtw == 2) GX_P(Q_, 2, 2); else GX_P(Q_, 2, 1); } \
                       else { if (rtw == 2) GX_P(Q_, 1, 2); else GX_P(Q_, 1, 1); } } while (0)
   const int role = p.epi == EPI_QKV ? 1 : (p.epi == EPI_ADD ? (p.K > p.N ? 3 : 2) : 0);
-#ifndef XS_ROLES
-#define XS_ROLES 1  // lab: 0 launches the untagged instantiations (A/B)
-#endif
-  if (XS_ROLES && role && !nt && xw == 8 && rtw == 1 && ((wdt == WDT_Q4 && p.M > 32 && pd == 1) || (wdt == WDT_BF16 && p.M <= 32 && pd == 2))) {
+  if (role && !nt && xw == 8 && rtw == 1 && ((wdt == WDT_Q4 && p.M > 32 && pd == 1) || (wdt == WDT_BF16 && p.M <= 32 && pd == 2))) {
 #define GX_R(Q_, MT_, PD_) do { if (role == 1) hipLaunchKernelGGL((gemm_xs_kernel<Q_, MT_, 1, PD_, false, 8, 1>), grid, dim3(512), 0, st, p); \
                                 else if (role == 2) hipLaunchKernelGGL((gemm_xs_kernel<Q_, MT_, 1, PD_, false, 8, 2>), grid, dim3(512), 0, st, p); \
                                 else hipLaunchKernelGGL((gemm_xs_kernel<Q_, MT_, 1, PD_, false, 8, 3>), grid, dim3(512), 0, st, p); } while (0)

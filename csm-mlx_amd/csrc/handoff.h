@@ -1,4 +1,5 @@
-// Inter-workgroup hand-off primitives of the persistent kernels (dec_frame.hip, bb_step.hip).
+// Inter-workgroup hand-off primitives of the persistent kernels (dec_frame.hip, bb_step.hip,
+// dec_step_xs.hip).
 // A value travels as one naturally aligned 8-byte granule {fp32 bits, tag} written by ONE agent-scope
 // relaxed (sc1) store and read with agent-scope relaxed (sc1) loads until the tag matches
 // (MI355X_MICROARCH.md, inter-workgroup visibility and the hand-off price list).
@@ -54,20 +55,28 @@ __device__ __forceinline__ u32x4_t bload(const void* base, int voff, int soff) {
   return __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, AUX));
 }
 
+// The bounded-spin test of every hand-off wait: true once `spin` reaches `limit`, or -- looked at
+// every 256 spins -- once another workgroup has raised the error word; either way the word is raised
+// and the caller stops waiting (results garbage, the host raises), so the grid always drains.
+__device__ __forceinline__ bool spin_fail(int* err, unsigned limit, unsigned spin) {
+  if (spin >= limit || ((spin & 255) == 255 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+    __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return true;
+  }
+  return false;
+}
+
 // Wait until this thread's granules base[off[u]] (u < GPT, val[u]) carry `tag`, then use(probe).
-// TWO: two probes in flight, the second issued GAP sleeps after the first, each re-issued whole as
-// soon as its predecessor returns stale -- a probe returns every half round trip, so a hand-off is
-// seen about a quarter round trip sooner than by one probe re-polled on its return.  Every load is
-// unconditional (an unused entry reads granule 0 and counts as current) and use() runs on the exit
-// the matched probe left by: no branch around a load and no copy of a probe's registers at a merge,
-// so the compiler's vmcnt waits stay exact (a check waits for its own probe, the other stays in
-// flight).  A granule's tag only moves from stale to current during a wait (its buffer is rewritten
-// only after every workgroup has published the next hand-off), so any all-current probe is the
-// hand-off.  fail(spin): the bounded-spin / error-flag test.  DELAY: sleeps before the first probe
+// One probe, its stale granules re-polled.  The first probe's loads are unconditional (an unused
+// entry reads granule 0 and counts as current): no branch around a load, so the compiler's vmcnt
+// waits stay exact.  A granule's tag only moves from stale to current during a wait (its buffer is
+// rewritten only after every workgroup has published the next hand-off), so any all-current probe is
+// the hand-off.  fail(spin): the bounded-spin / error-flag test.  DELAY: sleeps before the first probe
 // (fewer wasted probes while the producers are still working); REPOLL: sleeps between re-polls.
-// Measured (profiles/r03_ab_poll.txt): TWO costs the frame decoder +12 % (every re-issued probe adds
-// sc1 traffic on the lines every workgroup polls), so both kernels keep one probe.
-template <int GPT, bool TWO, int GAP, int DELAY, int REPOLL, typename Fail, typename F>
+// Two probes in flight, each re-issued whole as soon as it returned stale, cost the frame decoder
+// +12 % (profiles/r03_ab_poll.txt): every re-issued probe adds sc1 traffic on the lines every
+// workgroup polls.
+template <int GPT, int DELAY, int REPOLL, typename Fail, typename F>
 __device__ __forceinline__ void poll_granules(const u64* base, const int (&off)[GPT], const bool (&val)[GPT], unsigned tag,
                                               Fail&& fail, F&& use) {
   auto cur = [&](const u64 (&x)[GPT]) {
@@ -76,39 +85,17 @@ __device__ __forceinline__ void poll_granules(const u64* base, const int (&off)[
     for (int u = 0; u < GPT; ++u) ok &= !val[u] || (unsigned)(x[u] >> 32) == tag;
     return ok;
   };
-  auto probe = [&](u64 (&x)[GPT]) {
-#pragma unroll
-    for (int u = 0; u < GPT; ++u) x[u] = gload(base + (val[u] ? off[u] : 0));
-  };
   if constexpr (DELAY > 0) __builtin_amdgcn_s_sleep(DELAY);
-  if constexpr (TWO) {
-    u64 a[GPT], b[GPT];
-    probe(a);
-    __builtin_amdgcn_s_sleep(GAP);
-    probe(b);
-    for (unsigned spin = 0;; spin += 2) {
-      if (cur(a) || fail(spin)) {
-        use(a);
-        break;
-      }
-      probe(a);
-      if (cur(b)) {
-        use(b);
-        break;
-      }
-      probe(b);
-    }
-  } else {
-    u64 g[GPT];
-    probe(g);
-    for (unsigned spin = 0; !cur(g) && !fail(spin); ++spin) {
-      __builtin_amdgcn_s_sleep(REPOLL);
+  u64 g[GPT];
 #pragma unroll
-      for (int u = 0; u < GPT; ++u)
-        if (val[u] && (unsigned)(g[u] >> 32) != tag) g[u] = gload(base + off[u]);
-    }
-    use(g);
+  for (int u = 0; u < GPT; ++u) g[u] = gload(base + (val[u] ? off[u] : 0));
+  for (unsigned spin = 0; !cur(g) && !fail(spin); ++spin) {
+    __builtin_amdgcn_s_sleep(REPOLL);
+#pragma unroll
+    for (int u = 0; u < GPT; ++u)
+      if (val[u] && (unsigned)(g[u] >> 32) != tag) g[u] = gload(base + off[u]);
   }
+  use(g);
 }
 
 // poll_granules over granule PAIRS: one 16-B sc1 load per pair (granules 2i, 2i + 1: their tags in
@@ -118,7 +105,7 @@ __device__ __forceinline__ void poll_granules(const u64* base, const int (&off)[
 // 16-B sc1 store of two granules) to be seen whole, never a fresh tag beside a stale value.  The HIP /
 // HSA memory model promises that only for aligned atomics of <= 8 B; on gfx950 under ROCm 7.2 16-B
 // sc1 accesses are observed untorn at 8-B halves, not as an architectural guarantee
-// (/opt/skills/guides/MI355X_MICROARCH.md, inter-workgroup visibility: "R2's granule ... also for 16-B
+// (MI355X_MICROARCH.md, inter-workgroup visibility: "R2's granule ... also for 16-B
 // sc1 halves").  The guard is the data: the 125-frame bf16 fixtures (tests/test_long_gpu.py) and the
 // determinism checks (tests/test_dec_frame_gpu.py) run every frame through these polls, and a torn
 // read would put a stale partial into a sum and change codes or logits.

@@ -100,7 +100,7 @@ def test_config4_shard_b32_greedy_125_frames():
     assert not errs, "; ".join(errs[:10])
 
 
-def test_config3_stream_b32_sampled_64_frames():
+def test_config3_stream_b32_sampled_125_frames():
     from csm_mlx.generation import stream_generate_batch
     from test_configs_gpu import _codec, _engine_codes
     z = _fixture("config3_b32_stream_125.npz")

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of abl/libcsm_hip_<v>.so builds (tools/variant.sh) in one GPU call: a short bench line each,
+# A/B of lab/libcsm_hip_<v>.so builds (tools/variant.sh) in one GPU call: a short bench line each,
 # printing frames/s and the live dec_frame / bb_step (or GEMM) averages.
 # usage: tools/ab.sh [-c N] v1 v2 ...   (an entry v@VAR=value also sets an environment variable)
 set -o pipefail

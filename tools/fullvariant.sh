@@ -1,16 +1,17 @@
 #!/bin/bash
-# Build a whole-library A/B variant (every source recompiled with extra -D flags, e.g. a header
-# switch such as -DXS_F32=0): abl/libcsm_hip_<name>.so.  usage: tools/fullvariant.sh <name> <flags...>
+# Build a whole-library A/B variant: every source recompiled with the product's own flags (csm_mlx/_build.py)
+# plus extra ones (e.g. a profiling switch of a shared header): lab/libcsm_hip_<name>.so.
+# usage: tools/fullvariant.sh <name> <flags...>   (VARIANT_DIR=<dir> writes there)
 set -e
 name=$1; shift
+OUT=${VARIANT_DIR:-lab}
 cd "$(dirname "$0")/.."
-b=/tmp/fv_$name; mkdir -p $b abl
+b=/tmp/fv_$name; mkdir -p $b $OUT
+pids=""
 for src in csm-mlx_amd/csrc/*.hip csm-mlx_amd/csrc/*.cpp; do
-  f=$(basename $src); extra=""
-  case $f in dec_frame.hip|bb_step.hip) extra="-mllvm -amdgpu-use-amdgpu-trackers=1";; esac
-  lang=""; case $f in *.hip) lang="-x hip";; esac
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-result $extra "$@" -Icsm-mlx_amd/csrc $lang -c $src -o $b/$f.o &
+  f=$(basename $src)
+  python csm-mlx_amd/csm_mlx/_build.py compile $f $b/$f.o "$@" & pids="$pids $!"
 done
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o abl/libcsm_hip_$name.so $b/*.o
-echo abl/libcsm_hip_$name.so
+for p in $pids; do wait $p; done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/libcsm_hip_$name.so $b/*.o
+echo $OUT/libcsm_hip_$name.so

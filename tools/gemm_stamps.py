@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Phase clocks of the batched MFMA GEMM (lab build: tools/variant.sh st gemm_kernels.hip -DGEMM_STAMPS,
-run with CSM_HIP_LIB=abl/libcsm_hip_st.so): per projection at M rows, the mean over blocks of
+run with CSM_HIP_LIB=lab/libcsm_hip_st.so): per projection at M rows, the mean over blocks of
 [prologue (first stage staged), K loop, publish + ticket, combine + epilogue (last slice)] in us,
 and the launch span (first block start -> last block end).
 usage: python tools/gemm_stamps.py bf16|q4 M"""
