@@ -4,8 +4,8 @@
 signatures (generation.py:21-31, 95-105, 181-191) plus the ``sampler=`` keyword
 the reference README/CLI pass (README.md:49; cli/generate.py:197-199).  The
 frame step itself runs as two captured HIP graphs inside libcsm_hip.so
-(csm-mlx_amd/csrc/csm_engine.hip); the host only assembles prompts, polls EOS
-flags every ``chunk`` frames and hands the code history to the Mimi decoder,
+(csm-mlx_amd/csrc/csm_engine.hip and its csm_engine_*.hip siblings); the
+host only assembles prompts, polls EOS flags every ``chunk`` frames and hands the code history to the Mimi decoder,
 which reads it straight from device memory.
 
 ``generate_batch`` is the batched extension used by bench.py: B independent

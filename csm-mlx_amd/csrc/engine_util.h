@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -35,6 +36,12 @@ void csm_set_error(const std::string& msg);
     return CSM_ERR_HIP;                                             \
   }                                                                 \
   return CSM_OK;
+
+// A switch that is on unless its environment variable starts with '0' (CSM_DEC_FRAME=0, ...)
+inline bool env_on(const char* name) {
+  const char* v = getenv(name);
+  return !(v && v[0] == '0');
+}
 
 // Convert n host elements of src_dtype (CSM_F32 / CSM_BF16) to the storage dtype (0 f32, 1 bf16).
 std::vector<uint8_t> convert_to(const void* src, int src_dtype, size_t n, int dst_wdt);
