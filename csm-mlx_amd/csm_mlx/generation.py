@@ -299,11 +299,10 @@ def generate_codes_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndar
             if cache.run_processed(logits_processors, c0_history):
                 break
         left = 0
-    ahead = os.environ.get("CSM_EOS_AHEAD", "1") != "0"   # lab: 0 = poll each chunk after it ends (A/B)
     while left > 0:
-        n = min(chunk if ahead else 2 * chunk, left)
-        ended = cache.run_ahead(n) if ahead else cache.run(n)   # EOS poll (generation.py:151); ahead: of the
-        left -= n                                               # previous chunk, while this one runs
+        n = min(chunk, left)
+        ended = cache.run_ahead(n)          # EOS poll (generation.py:151) of the previous chunk, while
+        left -= n                           # this one runs
         if ended:                           # (this chunk's frames then change no returned code)
             break
     hist, n_frames, _ = cache.codes()

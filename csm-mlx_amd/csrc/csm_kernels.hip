@@ -310,7 +310,6 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvParams p) {
 // LDS once, reducing sum(x^2) per row once per block, (3) runs the dot products from LDS.  Per
 // thread the weight K-slices, accumulation order and pair epilogues are those of gemv_kernel.
 constexpr int XL_KMAX = 2048;
-constexpr int XL_KMAX_WIDE = 8192;  // down projections (K = 8192) at M = 1: 32 KB of LDS
 
 template <typename WT, int G, int RPT, int MT, int TAG, int KMAX = XL_KMAX>
 __global__ __launch_bounds__(256) void gemv_xl_kernel(GemvParams p) {
@@ -1382,48 +1381,31 @@ __global__ void advance_kernel(AdvanceParams p) {
 // row group (G = 64: no cross-wave reduction, 2-4 K-steps per thread); the K = 8192 down
 // projections want the whole block on a row pair (G = 256 at N = 1024, 128 at N = 2048); every
 // other shape is latency-bound and best at G = 128 (K >= 1024).  RPT = 2 wins everywhere at M = 1.
-// LDS-staged activations for the decode regime (gemv_xl_kernel): 1 = on for K <= 2048, 3 = also the
-// K = 8192 down projections (measured slower: dec down 5.96 vs 5.77 us, 231.6 vs 234.8 frames/s),
-// 0 = off.  CSM_GEMV_XL overrides the default (A/B runs; read once per process).
-static const int g_gemv_xl = [] { const char* e = getenv("CSM_GEMV_XL"); return e ? atoi(e) : 1; }();
+// LDS-staged activations for the decode regime (gemv_xl_kernel) for K <= 2048; staging the K = 8192
+// down projections too measured slower (dec down 5.96 vs 5.77 us, 231.6 vs 234.8 frames/s).
+constexpr int GEMV_RPT = 2;
 
-static void gemv_tiling(int N, int K, int M, int& G, int& RPT) {
-  (void)M;
-  if (N >= 8192) G = 64;
-  else if (K >= 8192) G = N <= 1024 ? 256 : 128;
-  else G = K >= 1024 ? 128 : 64;
-  RPT = 2;
+static int gemv_tiling(int N, int K) {  // G
+  if (N >= 8192) return 64;
+  if (K >= 8192) return N <= 1024 ? 256 : 128;
+  return K >= 1024 ? 128 : 64;
 }
 
 template <typename WT, int TAG>
 static void launch_gemv_t(const GemvParams& p, hipStream_t st) {
-  int G, RPT;
-  gemv_tiling(p.N, p.K, p.M, G, RPT);
-  const int blocks = p.N / ((256 / G) * RPT);
+  const int G = gemv_tiling(p.N, p.K);
+  const int blocks = p.N / ((256 / G) * GEMV_RPT);
   const bool mt1 = p.M == 1;
-  const bool xl = g_gemv_xl && p.M <= 4 && p.K <= XL_KMAX && p.K % 8 == 0;
-  // K = 8192 at M = 1 (down projections): LDS-staged x, every weight K-step in flight first
-  const bool xlw = (g_gemv_xl & 2) != 0 && mt1 && p.K > XL_KMAX && p.K <= XL_KMAX_WIDE && p.K % 8 == 0 &&
-                   G >= 128;
-  if (xlw && G == 256 && RPT == 2) {
-    hipLaunchKernelGGL((gemv_xl_kernel<WT, 256, 2, 1, TAG, XL_KMAX_WIDE>), dim3(blocks), dim3(256), 0, st, p);
-    return;
-  }
-  if (xlw && G == 128 && RPT == 2) {
-    hipLaunchKernelGGL((gemv_xl_kernel<WT, 128, 2, 1, TAG, XL_KMAX_WIDE>), dim3(blocks), dim3(256), 0, st, p);
-    return;
-  }
-#define GEMV_L(G_, R_, M_)                                                                            \
-  do {                                                                                                \
-    if (xl) hipLaunchKernelGGL((gemv_xl_kernel<WT, G_, R_, M_, TAG>), dim3(blocks), dim3(256), 0, st, p); \
-    else hipLaunchKernelGGL((gemv_kernel<WT, G_, R_, M_, TAG>), dim3(blocks), dim3(256), 0, st, p);  \
+  const bool xl = p.M <= 4 && p.K <= XL_KMAX && p.K % 8 == 0;
+#define GEMV_L(G_, M_)                                                                                       \
+  do {                                                                                                       \
+    if (xl) hipLaunchKernelGGL((gemv_xl_kernel<WT, G_, GEMV_RPT, M_, TAG>), dim3(blocks), dim3(256), 0, st, p); \
+    else hipLaunchKernelGGL((gemv_kernel<WT, G_, GEMV_RPT, M_, TAG>), dim3(blocks), dim3(256), 0, st, p);    \
   } while (0)
-#define GEMV_M(G_, R_) do { if (mt1) GEMV_L(G_, R_, 1); else GEMV_L(G_, R_, 4); } while (0)
-#define GEMV_R(G_) do { if (RPT == 4) GEMV_M(G_, 4); else GEMV_M(G_, 2); } while (0)
-  if (G == 256) GEMV_R(256);
-  else if (G == 128) GEMV_R(128);
-  else GEMV_R(64);
-#undef GEMV_R
+#define GEMV_M(G_) do { if (mt1) GEMV_L(G_, 1); else GEMV_L(G_, 4); } while (0)
+  if (G == 256) GEMV_M(256);
+  else if (G == 128) GEMV_M(128);
+  else GEMV_M(64);
 #undef GEMV_M
 #undef GEMV_L
 }
@@ -1435,19 +1417,15 @@ int gemv_partials(int N, int K, int M, int wdt) {
 }
 
 int gemv_rows_per_block(int N, int K, int M) {
-  int G, RPT;
-  gemv_tiling(N, K, M, G, RPT);
-  return (256 / G) * RPT;
+  (void)M;
+  return (256 / gemv_tiling(N, K)) * GEMV_RPT;
 }
 
-// Weight-load cache policy per stack tag (bit t set -> non-temporal loads for tag t).  The
-// backbone streams 1.95 GB per frame once; the decoder's 221 MB are re-read 31x per frame and
-// can stay resident in the 256 MiB Infinity Cache if the backbone stream does not evict them.
-// CSM_NT_MASK overrides the default (A/B runs; read once per process).
-static int gemv_nt_mask() {
-  static const int m = [] { const char* e = getenv("CSM_NT_MASK"); return e ? atoi(e) : 5; }();  // backbone + heads (measured: 209.9 vs 202.0 fps all-default)
-  return m;
-}
+// Weight-load cache policy per stack tag: non-temporal loads for the backbone (tag 0) and the heads
+// (tag 2).  The backbone streams 1.95 GB per frame once; the decoder's 221 MB are re-read 31x per
+// frame and can stay resident in the 256 MiB Infinity Cache if the backbone stream does not evict
+// them (measured: 209.9 vs 202.0 fps with default loads everywhere).
+bool gemv_nt(int tag) { return tag == 0 || tag == 2; }
 
 // Folded-table builds (csm_engine.hip build_proj_table): every row of a table in ONE launch of
 // gemv_xl_kernel<WT, 128, 2, MT, 1, KMAX> with grid.y over chunks of MT rows (MT = 14 at K <= 1024,
@@ -1455,10 +1433,8 @@ static int gemv_nt_mask() {
 // K-slices, reduction order and epilogue for every MT; without a norm also gemv_kernel's).  Other
 // shapes / weight types fall back to launch_gemv in chunks of 4 rows.
 int gemv_table_rows(int N, int K, int wdt, int tag) {
-  int G, RPT;
-  gemv_tiling(N, K, 1, G, RPT);
-  const bool ok = g_gemv_xl && (wdt == WDT_BF16 || wdt == WDT_F32) && K <= 2048 && K % 8 == 0 && G == 128 &&
-                  RPT == 2 && tag == 1 && !((gemv_nt_mask() >> tag) & 1);
+  const bool ok = (wdt == WDT_BF16 || wdt == WDT_F32) && K <= 2048 && K % 8 == 0 && gemv_tiling(N, K) == 128 &&
+                  tag == 1;
   return ok ? (K <= 1024 ? 14 : 7) : 4;
 }
 void launch_gemv_table(const GemvParams& p0, int wdt, int epi, int norm, hipStream_t st, int tag) {
@@ -1489,14 +1465,14 @@ void launch_gemv(const GemvParams& p0, int wdt, int epi, int norm, hipStream_t s
   GemvParams p = p0;
   p.epi = epi;
   if (!norm) p.nw = nullptr;
-  const bool nt = (gemv_nt_mask() >> tag) & 1;
+  const bool nt = gemv_nt(tag);
   if (!p.xpart && !p.x_copy && !p.no_mfma && gemm_mfma_eligible(p.N, p.K, p.M, wdt)) {
     launch_gemm_mfma(p, wdt, nt, st);
   } else if (wdt == WDT_Q4) {
     launch_gemv_q4(p, nt, st);
   } else if (wdt == WDT_BF16) {
-    if (tag == 1) nt ? launch_gemv_t<bf16_t, 5>(p, st) : launch_gemv_t<bf16_t, 1>(p, st);
-    else if (tag == 2) nt ? launch_gemv_t<bf16_t, 6>(p, st) : launch_gemv_t<bf16_t, 2>(p, st);
+    if (tag == 1) launch_gemv_t<bf16_t, 1>(p, st);
+    else if (tag == 2) launch_gemv_t<bf16_t, 6>(p, st);
     else nt ? launch_gemv_t<bf16_t, 4>(p, st) : launch_gemv_t<bf16_t, 0>(p, st);
   } else {
     if (tag == 1) launch_gemv_t<float, 1>(p, st);
@@ -1528,14 +1504,12 @@ void launch_embed(const EmbedParams& p, int wdt, int M, hipStream_t st) {
   else hipLaunchKernelGGL(embed_rows_kernel<float>, grid, dim3(64), 0, st, p);
 }
 
-static bool g_attn_short = [] { const char* e = getenv("CSM_ATTN_SHORT"); return !(e && e[0] == '0'); }();
-
 void launch_attn(const AttnParams& p, int hd, hipStream_t st) {
   if (p.xs_out && p.g_tab && !(hd == 128 && p.mode == ATTN_CAUSAL && p.S_cap <= 32)) {
     fprintf(stderr, "csm: table-gathered attention with split output only on the depth decoder's short attention\n");
     abort();
   }
-  if ((g_attn_short || (p.xs_out && p.g_tab)) && hd == 128 && p.mode == ATTN_CAUSAL && p.S_cap <= 32) {  // depth decoder
+  if (hd == 128 && p.mode == ATTN_CAUSAL && p.S_cap <= 32) {  // depth decoder
     hipLaunchKernelGGL((attn_short_kernel<128, 32>), dim3(p.M * p.Hq), dim3(64), 0, st, p);
     return;
   }
@@ -1546,9 +1520,8 @@ void launch_attn(const AttnParams& p, int hd, hipStream_t st) {
     return;
   }
   // the codec transformer's whole-call rows (Mimi encode / decode: rm.T rows per utterance, every key of
-  // the call visible): the same matrix-core tiles, tiles derived from rm.T (CSM_MIMI_ATTN_TILES=0: per row)
-  static const bool mimi_tiles = [] { const char* e = getenv("CSM_MIMI_ATTN_TILES"); return !(e && e[0] == '0'); }();
-  if (mimi_tiles && !p.rm.tiles && !p.rm.row_b && !p.rm.row_pos && p.mode == ATTN_BLOCK && hd == 64 && !p.g_tab &&
+  // the call visible): the same matrix-core tiles, tiles derived from rm.T
+  if (!p.rm.tiles && !p.rm.row_b && !p.rm.row_pos && p.mode == ATTN_BLOCK && hd == 64 && !p.g_tab &&
       !p.xs_out && p.rm.T >= 16 && p.M % p.rm.T == 0 && p.Hq / p.Hkv <= 4) {
     AttnParams q = p;
     q.rm.ntiles = p.M / p.rm.T * ((p.rm.T + 63) / 64);
@@ -1566,8 +1539,6 @@ void launch_rmsnorm_rows(const float* x, int xs, const float* w, float eps, int 
 }
 
 int wdc_chunk(int D) { return D == 1024 ? 16 : (D == 2048 ? 8 : 0); }
-
-bool gemv_nt(int tag) { return (gemv_nt_mask() >> tag) & 1; }
 
 void launch_sample(const SampleParams& p, int wdt, int B, hipStream_t st) {
   if (p.V > 256 * SAMPLE_NPT) {

@@ -468,17 +468,12 @@ __global__ __launch_bounds__(64 * NW) void gemm_wide_kernel(GemvParams p) {
 // backbone gate/up (the activation split shared by 8 row tiles outweighs the longer split-K combine);
 // 128 for the other wide int4 projections and the bf16 gate/up at 64 batch rows; 64 elsewhere.  K
 // slices are doubled until the grid has >= 256 blocks (every CU streaming) while each slice keeps
-// whole stages.  CSM_GEMM_NBR / CSM_GEMM_BLOCKS override (lab sweeps).
-static int g_nbr_env = [] { const char* e = getenv("CSM_GEMM_NBR"); return e ? atoi(e) : 0; }();
-static int g_blocks_env = [] { const char* e = getenv("CSM_GEMM_BLOCKS"); return e ? atoi(e) : 0; }();
+// whole stages.
 // int4 prompt prefill (>= 256 rows, the 8-wave blocks): 256 weight rows per block for every shape (the
 // block's activation staging -- norm, three-part split, group sums -- is shared by twice the columns):
-// config 5's prefill 0.155 -> 0.140 s (profiles/r04_ab_prefill_nbr.txt).  CSM_GEMM_PREFILL_NBR=0: the
-// per-shape widths below.
-static int g_prefill_nbr = [] { const char* e = getenv("CSM_GEMM_PREFILL_NBR"); return e ? atoi(e) : 256; }();
+// config 5's prefill 0.155 -> 0.140 s against the per-shape widths below (profiles/r04_ab_prefill_nbr.txt).
 static int gemm_nbr(int N, int K, int M, bool q4) {
-  if (g_nbr_env == 64 || g_nbr_env == 128 || g_nbr_env == 256) return g_nbr_env;
-  if (q4 && M >= 256 && (g_prefill_nbr == 128 || g_prefill_nbr == 256)) return g_prefill_nbr;
+  if (q4 && M >= 256) return 256;
   if (q4) {
     if (N >= 8192 && K >= 2048) return 256;
     if (N >= 8192 || (N >= 2048 && (N >= 3072 || K >= 8192))) return 128;
@@ -486,7 +481,6 @@ static int gemm_nbr(int N, int K, int M, bool q4) {
   }
   return (N >= 8192 && M > 32) ? 128 : 64;
 }
-static int g_prefill_blocks = [] { const char* e = getenv("CSM_GEMM_PREFILL_BLOCKS"); return !e || atoi(e) != 0; }();
 static int gemm_ksplit(int N, int K, int M, bool q4) {
   const int nbr = gemm_nbr(N, K, M, q4);
   const int tiles = (N + nbr - 1) / nbr, chunks = (M + 63) / 64;
@@ -497,8 +491,8 @@ static int gemm_ksplit(int N, int K, int M, bool q4) {
   const bool half = (size_t)N * K <= (size_t)1536 * 1024 || (q4 && N == 3072 && K == 2048);
   // the int4 prompt prefill (>= 256 rows on 256-row blocks): 128 too (its o / down at 248 blocks then run
   // unsplit; profiles/r04_ab_prefill_blocks.txt)
-  const bool prefill = q4 && M >= 256 && g_prefill_blocks;
-  const int target = g_blocks_env > 0 ? g_blocks_env : ((half || prefill) ? 128 : 256);
+  const bool prefill = q4 && M >= 256;
+  const int target = (half || prefill) ? 128 : 256;
   int ks = 1;
   while (tiles * chunks * ks < target && ks < GK_MAX_SLICES && K % (GP_KC * ks * 2) == 0) ks *= 2;
   return ks;
@@ -523,12 +517,9 @@ static constexpr int gemm_pd_cap(bool q4, int mt, int nbr) { return nbr == 256 ?
 
 // 8-wave blocks (two waves per SIMD: one wave's activation staging and int4 fold beside the other's
 // MFMAs) for long prompts (>= GEMM_W8_MIN_M rows: the prompt prefill), where the 4-wave block holds
-// 256 VGPRs + AGPRs at one wave per SIMD.  CSM_GEMM_W8=0: always 4 (A/B).
+// 256 VGPRs + AGPRs at one wave per SIMD.
 constexpr int GEMM_W8_MIN_M = 256;
-static bool gemm_w8(int M) {
-  static const bool on = [] { const char* e = getenv("CSM_GEMM_W8"); return !e || atoi(e) != 0; }();
-  return on && M >= GEMM_W8_MIN_M;
-}
+static bool gemm_w8(int M) { return M >= GEMM_W8_MIN_M; }
 
 void launch_gemm_mfma(const GemvParams& p0, int wdt, bool nt, hipStream_t st) {
   GemvParams p = p0;

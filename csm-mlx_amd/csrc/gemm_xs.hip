@@ -491,37 +491,28 @@ void xs_shape(int N, int K, int M, bool head, int& rtw, int& ks, int& pd, int& x
   const int nks = K / XK;
   // long-K projections (down) on 32-row tiles: twice the tiles, half the split-K slices and a quarter of
   // the partial bytes to combine -- 12.1 vs 16.7 us for the decoder down at 32 rows (tools/gemm_bench.py)
-  static const int rtw_long = [] { const char* v = getenv("CSM_XS_LONGK_RTW"); return v ? atoi(v) : 1; }();
-  rtw = (N >= 4096 || head) ? 2 : (K >= 4096 ? rtw_long : 1);
+  rtw = (N >= 4096 || head) ? 2 : 1;
   const int tiles = (N + 32 * rtw - 1) / (32 * rtw);
-  // split-K slices until the grid has >= `target` blocks (CSM_XS_BLOCKS lab knob).  The depth decoder's
-  // small projections at <= 32 rows (QKV / o, N x K <= 1536 x 1024) take none (target 1,
-  // CSM_XS_SMALL_BLOCKS): one K slice over 8 waves, no partial exchange -- decoder QKV 7.2 -> 6.3 us,
-  // o 6.7 -> 6.2 us, config 4 4347 -> 4378 frames/s (profiles/r04_ab_step1_small.txt); the backbone's
-  // o (2048 x 2048) measured ~2 us slower that way and keeps its slices (profiles/r04_prof_config4_per_frame_final.txt)
-  static const int target = [] { const char* v = getenv("CSM_XS_BLOCKS"); return v ? atoi(v) : 256; }();
-  static const int small_target = [] { const char* v = getenv("CSM_XS_SMALL_BLOCKS"); return v ? atoi(v) : 1; }();
+  // split-K slices until the grid has >= 256 blocks.  The depth decoder's small projections at <= 32 rows
+  // (QKV / o, N x K <= 1536 x 1024) take none: one K slice over 8 waves, no partial exchange -- decoder
+  // QKV 7.2 -> 6.3 us, o 6.7 -> 6.2 us, config 4 4347 -> 4378 frames/s (profiles/r04_ab_step1_small.txt);
+  // the backbone's o (2048 x 2048) measured ~2 us slower that way and keeps its slices
+  // (profiles/r04_prof_config4_per_frame_final.txt)
   const bool dec_small = (size_t)N * K <= (size_t)1536 * 1024 && M <= 32 && !head;
-  // the arg-max heads (N not a multiple of 64: the padded vocabulary): CSM_XS_HEAD_BLOCKS lab knob
-  static const int head_target = [] { const char* v = getenv("CSM_XS_HEAD_BLOCKS"); return v ? atoi(v) : 256; }();
-  const int tgt = dec_small ? small_target : (head && N % 64 != 0 ? head_target : target);
+  const int tgt = dec_small ? 1 : 256;
   // waves per block; the block's K slice is split between them.  4 (one per SIMD of the CU the block
   // occupies) against 2: QKV 9.4 -> 7.2 us and o 8.0 -> 6.8 us at 32 bf16 rows, int4 gate/up 24.7 -> 16.1
   // and down 20.6 -> 16.1 us at 64 rows; config 4 3667 -> 3816, config 5 3501 -> 4035 frames/s
   // (profiles/r04_ab_xs_waves.txt).  8 (two per SIMD: one wave's loads / int4 fold overlap the other's
-  // MFMAs) everywhere but the depth decoder's QKV / o at <= 32 rows (o 6.8 vs 7.2 us): gate/up 13.1 -> 11.6
-  // and down 12.3 -> 11.3 us at 32 bf16 rows, int4 gate/up 16.1 -> 13.8, down 15.5 -> 13.8, QKV 10.6 ->
-  // 9.8 us at 64 rows, the backbone's projections 4-14 % (profiles/r04_ab_xs_waves8.txt).  Lab knob
-  // CSM_XS_WAVES=2 / 4 / 8 forces one count everywhere.
-  static const int waves = [] { const char* v = getenv("CSM_XS_WAVES"); const int w = v ? atoi(v) : 0; return w == 2 || w == 4 || w == 8 ? w : 0; }();
-  // the heads (arg-max epilogue, 64-row tiles, ~33 of them): fewer waves per block leave room for
-  // more K slices, spreading the head's bytes over more CUs (CSM_XS_HEAD_WAVES lab knob).  4 waves (4 K
+  // MFMAs): gate/up 13.1 -> 11.6 and down 12.3 -> 11.3 us at 32 bf16 rows, int4 gate/up 16.1 -> 13.8, down
+  // 15.5 -> 13.8, QKV 10.6 -> 9.8 us at 64 rows, the backbone's projections 4-14 %
+  // (profiles/r04_ab_xs_waves8.txt); the decoder's QKV / o at <= 32 rows took 4 with split-K (o 6.8 vs
+  // 7.2 us) and take 8 now that they have one K slice.
+  // The arg-max heads (N not a multiple of 64: the padded vocabulary; 64-row tiles, ~33 of them): fewer
+  // waves per block leave room for more K slices, spreading the head's bytes over more CUs.  4 waves (4 K
   // slices, 132 blocks at 32 rows) against 8 (2 slices, 66 blocks): config 4 4383-4409 -> 4496 frames/s,
   // config 5 5408 -> 5413; 2 waves 4352-4435 (profiles/r05_ab_head_waves.txt)
-  static const int head_waves = [] { const char* v = getenv("CSM_XS_HEAD_WAVES"); const int w = v ? atoi(v) : 0; return w == 2 || w == 4 || w == 8 ? w : 4; }();
-  // (the decoder's QKV / o at <= 32 rows: 8 waves now that they take one K slice; 4 with split-K)
-  static const int small_waves = [] { const char* v = getenv("CSM_XS_SMALL_WAVES"); const int w = v ? atoi(v) : 0; return w == 2 || w == 4 || w == 8 ? w : 8; }();
-  const int want = waves ? waves : (head && N % 64 != 0 ? head_waves : (dec_small ? small_waves : 8));
+  const int want = head && N % 64 != 0 ? 4 : 8;
   xw = nks >= 2 * want ? want : (nks >= 8 ? 4 : 2);
   // every wave takes wst = nks / ks / xw whole stages: the waves must divide the slice's stages (K = 640:
   // 10 stages -> 2 waves), or the leftover stages would never be computed (gemm_xs_eligible rejects a
@@ -531,9 +522,8 @@ void xs_shape(int N, int K, int M, bool head, int& rtw, int& ks, int& pd, int& x
   while (tiles * ks < tgt && ks < MAX_SLICES && nks / (ks * 2) >= xw && nks % (ks * 2) == 0 && (nks / (ks * 2)) % xw == 0)
     ks *= 2;
   const int wst = nks / ks / xw;
-  // ring depth at 64 rows with 64-row tiles (lab knob CSM_XS_PD64, default 1: register budget)
-  static const int cap64 = [] { const char* v = getenv("CSM_XS_PD64"); return v ? std::max(1, atoi(v)) : 1; }();
-  int cap = M > 32 ? (rtw == 2 ? cap64 : 2) : 4;
+  // ring depth: 1 stage at 64 rows with 64-row tiles (register budget)
+  int cap = M > 32 ? (rtw == 2 ? 1 : 2) : 4;
   if (xw == 8) cap = std::min(cap, M > 32 ? 1 : 2);  // two waves per SIMD: <= 256 registers, no spills
   pd = 1;
   while (pd * 2 <= cap && wst % (pd * 2) == 0) pd *= 2;

@@ -486,14 +486,10 @@ int mimi_create(const mimi_dims* dims, int device, int max_batch, int max_frames
     m->S_cap = std::max(m->S_cap, 2 * max_frames + 16);
     // the codec's stream at the lowest priority (the engine's at the highest), so a streaming decode_step
     // overlapping the frame engine yields the CUs to the engine's dependent launches: config 3 +0.4-0.5 %
-    // in two alternating pairs (profiles/r06_ab_stream_prio.txt).  CSM_STREAM_PRIO=0: default priorities
-    if (const char* v = getenv("CSM_STREAM_PRIO"); !v || atoi(v) != 0) {
-      int least = 0, greatest = 0;
-      HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-      HIPCHK(hipStreamCreateWithPriority(&m->st, hipStreamNonBlocking, least));
-    } else {
-      HIPCHK(hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking));
-    }
+    // in two alternating pairs against default priorities (profiles/r06_ab_stream_prio.txt)
+    int least = 0, greatest = 0;
+    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIPCHK(hipStreamCreateWithPriority(&m->st, hipStreamNonBlocking, least));
     build_layout(m.get());
     m->rope = (float*)m->alloc((size_t)m->S_cap * hd * 4);
     const size_t kv = (size_t)max_batch * dims->num_heads * m->S_cap * hd * 4;
@@ -703,9 +699,8 @@ int mimi_encode_rows(mimi_codec* m, int B, int N, const float* pcm, const float*
       launch_linear(lp, st);
       const int k0 = q == 0 ? 0 : 1, k1 = q == 0 ? 1 : d.n_q;
       if (k1 <= k0) continue;
-      // many rows: one distance GEMM launch per codebook (CSM_RVQ_GEMM=0: the tiled / per-row kernels)
-      static const bool gemm_on = [] { const char* e = getenv("CSM_RVQ_GEMM"); return !(e && e[0] == '0'); }();
-      if (gemm_on && M >= 256 && rvq_gemm_eligible(cd, d.bins)) {
+      // many rows: one distance GEMM launch per codebook (profiles/r04_ab_rvq_gemm.txt), else a block per row
+      if (M >= 256 && rvq_gemm_eligible(cd, d.bins)) {
         grow(m->rvq_r, m->rvq_r_n, (size_t)2 * M * cd);
         grow(m->rvq_p, m->rvq_p_n, 2 * rvq_gemm_parts(M, d.bins));
         launch_rvq_encode_gemm(m->Rh, M, (int)Tf, cd, m->cb, m->cbT, m->c2half, d.bins, k0, k1, d.n_q, m->dcodes,

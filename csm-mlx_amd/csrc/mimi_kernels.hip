@@ -7,94 +7,6 @@
 #include "mimi_kernels.h"
 
 // ============================================================================ tiled GEMM core
-// out(i, j) = sum_kk A(i, kk) * B(kk, j); 64 x 64 tile, K-step 16, 4x4 outputs per thread.
-// Problems supply a(), b(), store(); B_KCONTIG selects the B-tile load mapping (consecutive kk
-// per thread when B's memory is contiguous along kk, else consecutive j).
-// SPLIT: blockIdx.z = z * ks + slice; the block sums K range [slice * KD / ks, (slice + 1) * KD / ks)
-// (whole 16-steps) and writes its raw tile to slab[slice][z][i][j]; splitk_reduce_kernel adds the slices
-// in order and runs the problem's epilogue.
-template <class P, bool SPLIT>
-__global__ __launch_bounds__(256) void gemm64_kernel(P p, int ks, float* slab, int Z) {
-  __shared__ __attribute__((aligned(16))) float As[16][68];
-  __shared__ __attribute__((aligned(16))) float Bs[16][68];
-  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-  const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
-  const int z = SPLIT ? (int)blockIdx.z / ks : (int)blockIdx.z, sl = SPLIT ? (int)blockIdx.z % ks : 0;
-  const int KD = p.kdim();
-  int kb = 0, ke = KD;
-  if constexpr (SPLIT) {
-    const int nst = (KD + 15) / 16;
-    kb = (nst * sl / ks) * 16;
-    ke = min(KD, (nst * (sl + 1) / ks) * 16);
-  }
-  float acc[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[r][c] = 0.f;
-  // the next K tile is fetched into registers while the current one is multiplied (one tile of
-  // prefetch hides the global-load latency that a load -> sync -> compute loop exposes per step)
-  float va[4], vb[4];
-  auto fetch = [&](int k0) {
-    {
-      const int i = tid >> 2, kq = (tid & 3) * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        va[e] = (i0 + i < p.M && k0 + kq + e < ke) ? p.a(z, i0 + i, k0 + kq + e) : 0.f;
-    }
-    if constexpr (P::B_KCONTIG) {
-      const int j = tid >> 2, kq = (tid & 3) * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        vb[e] = (j0 + j < p.N && k0 + kq + e < ke) ? p.b(z, k0 + kq + e, j0 + j) : 0.f;
-    } else {
-      const int kk = tid >> 4, jb = (tid & 15) * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        vb[e] = (k0 + kk < ke && j0 + jb + e < p.N) ? p.b(z, k0 + kk, j0 + jb + e) : 0.f;
-    }
-  };
-  fetch(kb);
-  for (int k0 = kb; k0 < ke; k0 += 16) {
-    {
-      const int i = tid >> 2, kq = (tid & 3) * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) As[kq + e][i] = va[e];
-    }
-    if constexpr (P::B_KCONTIG) {
-      const int j = tid >> 2, kq = (tid & 3) * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) Bs[kq + e][j] = vb[e];
-    } else {
-      const int kk = tid >> 4, jb = (tid & 15) * 4;
-      *reinterpret_cast<float4*>(&Bs[kk][jb]) = make_float4(vb[0], vb[1], vb[2], vb[3]);
-    }
-    __syncthreads();
-    if (k0 + 16 < ke) fetch(k0 + 16);
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-      const float4 a = *reinterpret_cast<const float4*>(&As[kk][ty * 4]);
-      const float4 b = *reinterpret_cast<const float4*>(&Bs[kk][tx * 4]);
-      const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[r][c] = fmaf(av[r], bv[c], acc[r][c]);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int i = i0 + ty * 4 + r, j = j0 + tx * 4 + c;
-      if (i < p.M && j < p.N) {
-        if constexpr (SPLIT) slab[(((size_t)sl * Z + z) * p.M + i) * p.N + j] = acc[r][c];
-        else p.store(z, i, j, acc[r][c]);
-      }
-    }
-}
-
 // Four consecutive floats at p as one 16-B load when p is 16-B aligned (else four 4-B loads): the
 // same values either way, fewer load instructions for the tile staging.
 __device__ __forceinline__ void ld4(const float* p, float (&v)[4]) {
@@ -107,14 +19,23 @@ __device__ __forceinline__ void ld4(const float* p, float (&v)[4]) {
   }
 }
 
-// The same tile on the matrix cores: v_mfma_f32_32x32x2_f32 (fp32 operands, fp32 accumulation; each
-// instruction adds its two products in k order with a rounding after each, as the fmaf chain above --
-// MI355X_MICROARCH.md, f32-input MFMA "exact f32 (= fmaf chain, bitwise)"), so every output is the
-// same fmaf chain over kk in order and the results equal gemm64_kernel's bit for bit.  Wave w owns
-// the 32 x 32 quadrant (w >> 1, w & 1): per K-step 8 MFMAs, operands one LDS dword per lane (lane
-// (r, h): A(i0 + 32 qi + r, k0 + 2t + h), B(k0 + 2t + h, j0 + 32 qj + r)); accumulator register q of
-// lane (r, h) holds output row 8 (q >> 2) + 4 h + (q & 3) of the quadrant, column r.  The im2col
-// staging (fetch) is unchanged: its VALU work for the next K-step runs beside the MFMAs.
+// out(i, j) = sum_kk A(i, kk) * B(kk, j); 64 x 64 tile, K-step 16, on the matrix cores.
+// Problems supply a(), b(), their 4-wide forms aptr() / b4() / b4k(), the epilogue pre() / post() and
+// store(); B_KCONTIG / kcontig() select the B-tile load mapping (consecutive kk per thread when B's
+// memory is contiguous along kk, else consecutive j).
+// SPLIT: blockIdx.z = z * ks + slice; the block sums K range [slice * KD / ks, (slice + 1) * KD / ks)
+// (whole 16-steps) and writes its raw tile to slab[slice][z][i][j]; splitk_reduce_kernel adds the slices
+// in order and runs the problem's epilogue.
+// v_mfma_f32_32x32x2_f32 (fp32 operands, fp32 accumulation) adds its two products in k order with a
+// rounding after each (MI355X_MICROARCH.md, f32-input MFMA "exact f32 (= fmaf chain, bitwise)"), so
+// every output is one fmaf chain over kk in order, bit for bit what the VALU tile this replaced gave
+// (profiles/r04_ab_mimi_mfma.txt).
+// Wave w owns the 32 x 32 quadrant (w >> 1, w & 1): per K-step 8 MFMAs, operands one LDS dword per
+// lane (lane (r, h): A(i0 + 32 qi + r, k0 + 2t + h), B(k0 + 2t + h, j0 + 32 qj + r)); accumulator register
+// q of lane (r, h) holds output row 8 (q >> 2) + 4 h + (q & 3) of the quadrant, column r.  The next K tile
+// is fetched into registers while the current one is multiplied (one tile of prefetch hides the
+// global-load latency that a load -> sync -> compute loop exposes per step); the im2col staging's VALU
+// work for the next K-step runs beside the MFMAs.
 template <class P, bool SPLIT>
 __global__ __launch_bounds__(256) void gemm64_mf_kernel(P p, int ks, float* slab, int Z) {
   typedef float f32x16_t __attribute__((ext_vector_type(16)));
@@ -349,25 +270,10 @@ __global__ __launch_bounds__(256) void gemm128_mf_kernel(P p, int ks, float* sla
     }
 }
 
-// CSM_MIMI_WIDE=0: every codec GEMM on the 64 x 64 tile (A/B); else launches of >= CSM_MIMI_WIDE_N columns
-// (default 256) and >= 192 wide blocks (fewer left CUs idle: a 4096-column decode conv ran 620 us on 128
-// blocks against 324 on 512 64-tiles), except 1-tap convs, take gemm128_mf_kernel
-// (profiles/r04_ab_mimi_wide.txt)
-static int mimi_wide_n() {
-  static const int v = [] {
-    const char* e = getenv("CSM_MIMI_WIDE");
-    if (e && atoi(e) == 0) return 1 << 30;
-    const char* n = getenv("CSM_MIMI_WIDE_N");
-    return n ? atoi(n) : 256;
-  }();
-  return v;
-}
-
-// CSM_MIMI_MFMA=0: the VALU tile (A/B)
-static bool mimi_mfma() {
-  static const bool v = [] { const char* e = getenv("CSM_MIMI_MFMA"); return !e || atoi(e) != 0; }();
-  return v;
-}
+// Launches of >= MIMI_WIDE_N columns and >= 192 wide blocks (fewer left CUs idle: a 4096-column decode
+// conv ran 620 us on 128 blocks against 324 on 512 64-tiles), except 1-tap convs, take
+// gemm128_mf_kernel (profiles/r04_ab_mimi_wide.txt)
+constexpr int MIMI_WIDE_N = 256;
 
 // the split-K slices of every output, added in slice order, then the problem's epilogue
 template <class P>
@@ -384,13 +290,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(P p, const float* sl
 
 // Split-K slices for a launch whose grid would hold `blocks` 64 x 64 tiles (counted on the batch-folded
 // column space, so a folded and an unfolded launch of the same conv split alike -- same sums): slices
-// double while the grid stays <= CSM_MIMI_KS_BLOCKS (default 512; 0 = never split) and every slice keeps
-// >= 64 of the K dimension.  The streaming decode_step's first conv (1024 x 64 outputs, K 3584) ran on
+// double while the grid stays <= 512 blocks and every slice keeps >= 64 of the K dimension.  The streaming decode_step's first conv (1024 x 64 outputs, K 3584) ran on
 // 16 blocks for 500 us (profiles/r04_prof_config3_per_frame.txt).
 static int mimi_splitk(int KD, int blocks, size_t slab_per_slice) {
-  static const int target = [] { const char* e = getenv("CSM_MIMI_KS_BLOCKS"); return e ? atoi(e) : 512; }();
   int ks = 1;
-  while (blocks * ks * 2 <= target && KD / (ks * 2) >= 64 && ks < 32 && slab_per_slice * ks * 2 <= MIMI_KS_WS_FLOATS) ks *= 2;
+  while (blocks * ks * 2 <= 512 && KD / (ks * 2) >= 64 && ks < 32 && slab_per_slice * ks * 2 <= MIMI_KS_WS_FLOATS) ks *= 2;
   return ks;
 }
 
@@ -412,24 +316,21 @@ static void launch_wide(const P& pr, dim3 grid, int ks, float* ws, hipStream_t s
 // exactly as the 64-tile one would: same sums)
 template <class P>
 static void launch_gemm64(const P& pr, dim3 grid, int ks, float* ws, hipStream_t st) {
-  const bool mf = mimi_mfma();
   const size_t wblocks = (size_t)((pr.N + 127) / 128) * ((pr.M + (pr.M <= 32 ? 31 : pr.M <= 64 ? 63 : 127)) /
                                                           (pr.M <= 32 ? 32 : pr.M <= 64 ? 64 : 128)) * grid.z;
-  if (mf && pr.wide_ok() && pr.N >= mimi_wide_n() && wblocks >= 192) {
+  if (pr.wide_ok() && pr.N >= MIMI_WIDE_N && wblocks >= 192) {
     if (pr.M <= 32) launch_wide<P, 32>(pr, grid, ks, ws, st);
     else if (pr.M <= 64) launch_wide<P, 64>(pr, grid, ks, ws, st);
     else launch_wide<P, 128>(pr, grid, ks, ws, st);
     return;
   }
   if (ks <= 1 || !ws) {
-    if (mf) hipLaunchKernelGGL((gemm64_mf_kernel<P, false>), grid, dim3(256), 0, st, pr, 1, nullptr, (int)grid.z);
-    else hipLaunchKernelGGL((gemm64_kernel<P, false>), grid, dim3(256), 0, st, pr, 1, nullptr, (int)grid.z);
+    hipLaunchKernelGGL((gemm64_mf_kernel<P, false>), grid, dim3(256), 0, st, pr, 1, nullptr, (int)grid.z);
     return;
   }
   const int Z = (int)grid.z;
   const dim3 g2(grid.x, grid.y, grid.z * ks);
-  if (mf) hipLaunchKernelGGL((gemm64_mf_kernel<P, true>), g2, dim3(256), 0, st, pr, ks, ws, Z);
-  else hipLaunchKernelGGL((gemm64_kernel<P, true>), g2, dim3(256), 0, st, pr, ks, ws, Z);
+  hipLaunchKernelGGL((gemm64_mf_kernel<P, true>), g2, dim3(256), 0, st, pr, ks, ws, Z);
   const size_t tot = (size_t)Z * pr.M * pr.N;
   const int rb = (int)std::min<size_t>(2048, (tot + 255) / 256);
   hipLaunchKernelGGL(splitk_reduce_kernel<P>, dim3(rb), dim3(256), 0, st, pr, ws, ks, Z);
@@ -658,14 +559,10 @@ struct LinProblem {
 // config 3 2932 -> 3076 frames/s (profiles/r03_ab_mimi.txt).  Round 4: above 16 rows the tiled GEMM
 // with split-K (mimi_splitk: 64-512 blocks instead of 8-32) -- the 64-row linears took 40-68 us on the
 // GEMV, which re-reads the weights for every 4-row pass (profiles/r04_prof_config3_per_frame.txt).
-// CSM_MIMI_GEMV_M sets the largest row count on the GEMV (0 = never).
-static int mimi_gemv_rows() {
-  static const int v = [] { const char* e = getenv("CSM_MIMI_GEMV_M"); return e ? atoi(e) : 16; }();
-  return v;
-}
+constexpr int MIMI_GEMV_ROWS = 16;  // the largest row count on the GEMV
 
 void launch_linear(const LinParams& p, hipStream_t st) {
-  if (!p.conv_T && p.M <= mimi_gemv_rows() && p.N % 8 == 0 && p.K % 8 == 0 &&
+  if (!p.conv_T && p.M <= MIMI_GEMV_ROWS && p.N % 8 == 0 && p.K % 8 == 0 &&
       p.N % gemv_rows_per_block(p.N, p.K, p.M) == 0 && gemv_rows_per_block(p.N, p.K, p.M) % 2 == 0) {
     GemvParams g{};
     g.W = p.W; g.N = p.N; g.K = p.K; g.x = p.x; g.xs = p.xs; g.M = p.M; g.out = p.out; g.os = p.os;
@@ -864,107 +761,10 @@ __global__ __launch_bounds__(256) void rvq_encode_kernel(float* r, int T, int cd
   for (int d = tid; d < cd; d += 256) r[(size_t)m * cd + d] = rs[d];
 }
 
-// Tiled encode for many rows: a block owns 16 latent rows (wave w: rows 4w..4w+3) and streams each
-// codebook through LDS in [32 dims][256 codes] tiles shared by all its rows -- the codebook is read
-// once per block instead of once per row.  Lane l of a wave scores codes 4l..4l+3 of every tile
-// against the wave's 4 rows (16 fp32 accumulators: one 16-B code read and one 16-B residual read
-// per 16 FMAs); the residuals sit transposed ([dim][row]) in LDS.  Every (row, code) dot is one
-// fmaf chain over the dims in order -- rvq_encode_kernel's arithmetic, so codes and residuals are
-// identical; the arg-min keeps the first minimum.
-constexpr int RVQ_RB = 16, RVQ_CC = 256, RVQ_DC = 32, RVQ_CDMAX = 512;
-__global__ __launch_bounds__(256) void rvq_encode_tiled_kernel(float* r, int M, int T, int cd, const float* cb,
-                                                               const float* c2half, int bins, int k0, int k1,
-                                                               int n_q, int* codes) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  __shared__ __attribute__((aligned(16))) float rsT[RVQ_CDMAX][RVQ_RB];   // residuals [dim][row]
-  __shared__ __attribute__((aligned(16))) float ct[RVQ_DC][RVQ_CC];       // codebook tile [dim][code]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m0 = blockIdx.x * RVQ_RB;
-  for (int e = tid; e < RVQ_RB * cd; e += 256) {
-    const int i = e / cd, d = e % cd;
-    rsT[d][i] = r[(size_t)min(m0 + i, M - 1) * cd + d];
-  }
-  __syncthreads();
-  for (int k = k0; k < k1; ++k) {
-    const float* cbk = cb + (size_t)k * bins * cd;
-    float best[4];
-    int bi[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      best[i] = INFINITY;
-      bi[i] = 0x7fffffff;
-    }
-    for (int c0 = 0; c0 < bins; c0 += RVQ_CC) {
-      float acc[4][4];  // [row][code]
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-      for (int d0 = 0; d0 < cd; d0 += RVQ_DC) {
-        const int dn = min(RVQ_DC, cd - d0);
-        __syncthreads();  // previous tile consumed
-        for (int e = tid; e < RVQ_CC * RVQ_DC; e += 256) {  // coalesced along dims
-          const int cc = e / RVQ_DC, dd = e % RVQ_DC;
-          const int c = c0 + cc;
-          ct[dd][cc] = (c < bins && dd < dn) ? cbk[(size_t)c * cd + d0 + dd] : 0.f;
-        }
-        __syncthreads();
-        for (int dd = 0; dd < dn; ++dd) {
-          const f4 a = *reinterpret_cast<const f4*>(&ct[dd][4 * lane]);
-          const f4 x = *reinterpret_cast<const f4*>(&rsT[d0 + dd][4 * wave]);
-          const float av[4] = {a.x, a.y, a.z, a.w}, xv[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(av[j], xv[i], acc[i][j]);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = c0 + 4 * lane + j;
-        if (c < bins) {
-          const float c2 = c2half[(size_t)k * bins + c];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float dist = c2 - acc[i][j];
-            if (dist < best[i]) {  // codes visited in increasing order: first minimum kept
-              best[i] = dist;
-              bi[i] = c;
-            }
-          }
-        }
-      }
-    }
-    // per row: first minimum over the wave's lanes, then the wave updates its rows' residuals
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float bv = best[i];
-      int bx = bi[i];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bx, o, 64);
-        if (ov < bv || (ov == bv && oi < bx)) {
-          bv = ov;
-          bx = oi;
-        }
-      }
-      bx = min(max(bx, 0), bins - 1);
-      const int m = m0 + 4 * wave + i;
-      if (lane == 0 && m < M) codes[((size_t)(m / T) * n_q + k) * T + m % T] = bx;
-      for (int d = lane; d < cd; d += 64) rsT[d][4 * wave + i] = rsT[d][4 * wave + i] - cbk[(size_t)bx * cd + d];
-    }
-  }
-  __syncthreads();
-  for (int e = tid; e < RVQ_RB * cd; e += 256) {
-    const int i = e / cd, d = e % cd;
-    if (m0 + i < M) r[(size_t)(m0 + i) * cd + d] = rsT[d][i];
-  }
-}
-
 // Split-RVQ encode as one distance GEMM per codebook (config 5's context encode: 4032 latent rows x 31
-// codebooks per 64 segments; rvq_encode_tiled_kernel streamed every codebook through every 16-row
-// block, 15 ms per launch).  Launch k: block (code tile ct of 256, row tile of 64) first finishes codebook
+// codebooks per 64 segments; a kernel that streamed every codebook through every 16-row block took 15 ms
+// per launch, profiles/r04_ab_rvq_gemm.txt).
+// Launch k: block (code tile ct of 256, row tile of 64) first finishes codebook
 // k-1 for its rows -- arg-min over the 8 code-tile partials of k-1 (first minimum), residual r_k = r_{k-1}
 // - c_{k-1}[idx] into LDS (every code tile of a row tile computes the same r_k; tile 0 writes it and the
 // code) -- then scores its 256 codes against the 64 rows: the (row, code) dots are fmaf chains over the
@@ -988,8 +788,10 @@ struct RvqStep {
   int M, T, cd, bins, nct, k, n_q;
 };
 
-// MF: the scores on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: each (row, code) dot the same
-// k-ordered fmaf chain, the product's operand order immaterial -- bit-identical codes).  Wave w scores
+// The scores run on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: each (row, code) dot the same
+// k-ordered fmaf chain, the product's operand order immaterial -- bit-identical codes to the VALU tile
+// this replaced, profiles/r04_ab_rvq_mfma.txt; MF stays in the signature so the kernel keeps its name in
+// traces).  Wave w scores
 // codes 64 w .. 64 w + 63 of the tile against all 64 rows (2 x 2 tiles of 32 x 32); odd dims of r_k and
 // of the codebook chunk are stored with the 32-column halves swapped, so the two k rows an operand read
 // touches (lanes h = 0 / 1) sit on disjoint LDS bank halves.
@@ -999,9 +801,10 @@ __global__ __launch_bounds__(256) void rvq_step_kernel(RvqStep p) {
   __shared__ __attribute__((aligned(16))) float rsT[RQ_CDMAX][RQ_R];      // r_k [dim][row]
   __shared__ __attribute__((aligned(16))) float Bs[2][RQ_D][RQ_C];        // codebook chunk [dim][code]
   __shared__ int sidx[RQ_R];
-  __shared__ unsigned long long wred[MF ? 4 : 1][RQ_R];
+  static_assert(MF, "the VALU scoring tile is retired");
+  __shared__ unsigned long long wred[4][RQ_R];
   const int tid = threadIdx.x, ct = blockIdx.x, m0 = blockIdx.y * RQ_R;
-  auto sw = [](int d) { return MF ? (d & 1) * 32 : 0; };  // column swizzle of dim d's row
+  auto sw = [](int d) { return (d & 1) * 32; };  // column swizzle of dim d's row
   const int cd = p.cd;
   // (1) finish codebook k-1 for the 64 rows
   if (tid < RQ_R) {
@@ -1024,8 +827,8 @@ __global__ __launch_bounds__(256) void rvq_step_kernel(RvqStep p) {
     if (ct == 0 && m0 + i < p.M) p.r_out[(size_t)m * cd + d] = v;
   }
   if (!p.part_cur) return;  // finishing pass (after the last codebook)
-  // (2) distances of this tile's 256 codes: thread (ty, tx) -> rows 8 ty .. +8, codes 8 tx .. +8
-  const int tx = tid & 31, ty = tid >> 5, c0 = ct * RQ_C;
+  // (2) distances of this tile's 256 codes
+  const int c0 = ct * RQ_C;
   auto load = [&](int buf, int d0) {
     for (int e = tid; e < RQ_D * RQ_C / 4; e += 256) {
       const int dd = e / (RQ_C / 4), c4 = (e % (RQ_C / 4)) * 4;
@@ -1033,104 +836,55 @@ __global__ __launch_bounds__(256) void rvq_step_kernel(RvqStep p) {
     }
   };
   const int nch = cd / RQ_D;
-  if constexpr (MF) {
-    typedef float f32x16_t __attribute__((ext_vector_type(16)));
-    const int lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    f32x16_t acc[2][2];
+  typedef float f32x16_t __attribute__((ext_vector_type(16)));
+  const int lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+  f32x16_t acc[2][2];
 #pragma unroll
-    for (int x = 0; x < 2; ++x)
+  for (int x = 0; x < 2; ++x)
 #pragma unroll
-      for (int y = 0; y < 2; ++y) acc[x][y] = f32x16_t{};
-    load(0, 0);
-    __syncthreads();
-    for (int ch = 0; ch < nch; ++ch) {
-      const int buf = ch & 1;
-      if (ch + 1 < nch) load(buf ^ 1, (ch + 1) * RQ_D);
-#pragma unroll 4
-      for (int t = 0; t < RQ_D / 2; ++t) {
-        const int dd = 2 * t + h, d = ch * RQ_D + dd;  // (RQ_D even: d and dd share their parity)
-        float a[2], b[2];
-#pragma unroll
-        for (int x = 0; x < 2; ++x) a[x] = rsT[d][(32 * x + r) ^ sw(d)];
-#pragma unroll
-        for (int y = 0; y < 2; ++y) b[y] = Bs[buf][dd][(64 * wave + 32 * y + r) ^ sw(dd)];
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-          for (int y = 0; y < 2; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[y], a[x], acc[x][y], 0, 0, 0);
-      }
-      __syncthreads();
-    }
-    // acc[x][y][q]: code 64 wave + 32 y + 8 (q >> 2) + 4 h + (q & 3), row 32 x + r (B operand = rows)
-    float c2[2][16];
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) c2[y][q] = p.c2half[c0 + 64 * wave + 32 * y + 8 * (q >> 2) + 4 * h + (q & 3)];
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-      unsigned long long best = ~0ull;
-#pragma unroll
-      for (int y = 0; y < 2; ++y)
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          best = min(best, rq_key(c2[y][q] - acc[x][y][q], c0 + 64 * wave + 32 * y + 8 * (q >> 2) + 4 * h + (q & 3)));
-      best = min(best, (unsigned long long)__shfl_xor(best, 32, 64));  // the other half's codes of this row
-      if (h == 0) wred[wave][32 * x + r] = best;
-    }
-    __syncthreads();
-    if (tid < RQ_R) {
-      const unsigned long long best = min(min(wred[0][tid], wred[1][tid]), min(wred[2][tid], wred[3][tid]));
-      if (m0 + tid < p.M) p.part_cur[(size_t)(m0 + tid) * p.nct + ct] = best;
-    }
-    return;
-  }
-  float acc[8][8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
+    for (int y = 0; y < 2; ++y) acc[x][y] = f32x16_t{};
   load(0, 0);
   __syncthreads();
   for (int ch = 0; ch < nch; ++ch) {
     const int buf = ch & 1;
     if (ch + 1 < nch) load(buf ^ 1, (ch + 1) * RQ_D);
 #pragma unroll 4
-    for (int dd = 0; dd < RQ_D; ++dd) {
-      const int d = ch * RQ_D + dd;
-      const f4 r0 = *reinterpret_cast<const f4*>(&rsT[d][8 * ty]);
-      const f4 r1 = *reinterpret_cast<const f4*>(&rsT[d][8 * ty + 4]);
-      const f4 b0 = *reinterpret_cast<const f4*>(&Bs[buf][dd][8 * tx]);
-      const f4 b1 = *reinterpret_cast<const f4*>(&Bs[buf][dd][8 * tx + 4]);
-      const float rv[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-      const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+    for (int t = 0; t < RQ_D / 2; ++t) {
+      const int dd = 2 * t + h, d = ch * RQ_D + dd;  // (RQ_D even: d and dd share their parity)
+      float a[2], b[2];
 #pragma unroll
-      for (int i = 0; i < 8; ++i)
+      for (int x = 0; x < 2; ++x) a[x] = rsT[d][(32 * x + r) ^ sw(d)];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = fmaf(bv[j], rv[i], acc[i][j]);
+      for (int y = 0; y < 2; ++y) b[y] = Bs[buf][dd][(64 * wave + 32 * y + r) ^ sw(dd)];
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[y], a[x], acc[x][y], 0, 0, 0);
     }
     __syncthreads();
   }
-  // (3) per row: first minimum over the tile's codes (keys: dist, then code)
+  // acc[x][y][q]: code 64 wave + 32 y + 8 (q >> 2) + 4 h + (q & 3), row 32 x + r (B operand = rows)
+  float c2[2][16];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
+  for (int y = 0; y < 2; ++y)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) c2[y][q] = p.c2half[c0 + 64 * wave + 32 * y + 8 * (q >> 2) + 4 * h + (q & 3)];
+#pragma unroll
+  for (int x = 0; x < 2; ++x) {
     unsigned long long best = ~0ull;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = c0 + 8 * tx + j;
-      best = min(best, rq_key(p.c2half[c] - acc[i][j], c));
-    }
+    for (int y = 0; y < 2; ++y)
 #pragma unroll
-    for (int o = 16; o > 0; o >>= 1) best = min(best, (unsigned long long)__shfl_xor(best, o, 32));
-    const int m = m0 + 8 * ty + i;
-    if (tx == 0 && m < p.M) p.part_cur[(size_t)m * p.nct + ct] = best;
+      for (int q = 0; q < 16; ++q)
+        best = min(best, rq_key(c2[y][q] - acc[x][y][q], c0 + 64 * wave + 32 * y + 8 * (q >> 2) + 4 * h + (q & 3)));
+    best = min(best, (unsigned long long)__shfl_xor(best, 32, 64));  // the other half's codes of this row
+    if (h == 0) wred[wave][32 * x + r] = best;
   }
-}
-
-// CSM_RVQ_MFMA=0: the VALU scoring tile (A/B)
-static bool rvq_mfma() {
-  static const bool v = [] { const char* e = getenv("CSM_RVQ_MFMA"); return !e || atoi(e) != 0; }();
-  return v;
+  __syncthreads();
+  if (tid < RQ_R) {
+    const unsigned long long best = min(min(wred[0][tid], wred[1][tid]), min(wred[2][tid], wred[3][tid]));
+    if (m0 + tid < p.M) p.part_cur[(size_t)(m0 + tid) * p.nct + ct] = best;
+  }
 }
 
 bool rvq_gemm_eligible(int cd, int bins) { return cd % RQ_D == 0 && cd <= RQ_CDMAX && bins % RQ_C == 0; }
@@ -1155,20 +909,12 @@ void launch_rvq_encode_gemm(float* r, int M, int T, int cd, const float* cb, con
     s.cbT = k < k1 ? cbT + (size_t)k * bins * cd : nullptr;
     s.c2half = k < k1 ? c2half + (size_t)k * bins : nullptr;
     // the finishing pass needs only code tile 0 (it writes the codes and r); it computes no distances
-    if (rvq_mfma()) hipLaunchKernelGGL(rvq_step_kernel<true>, k == k1 ? dim3(1, grid.y) : grid, dim3(256), 0, st, s);
-    else hipLaunchKernelGGL(rvq_step_kernel<false>, k == k1 ? dim3(1, grid.y) : grid, dim3(256), 0, st, s);
+    hipLaunchKernelGGL(rvq_step_kernel<true>, k == k1 ? dim3(1, grid.y) : grid, dim3(256), 0, st, s);
   }
 }
 
 void launch_rvq_encode(float* r, int M, int T, int cd, const float* cb, const float* c2half, int bins, int k0, int k1,
                        int n_q, int* codes, hipStream_t st) {
-  const char* env = getenv("CSM_RVQ_TILED");  // read per call (encode is never graph-captured): A/B tests
-  const int mode = env ? atoi(env) : 1;
-  if (mode && cd <= RVQ_CDMAX && M >= 1024) {  // tiled once there are >= 64 blocks of 16 rows
-    hipLaunchKernelGGL(rvq_encode_tiled_kernel, dim3((M + RVQ_RB - 1) / RVQ_RB), dim3(256), 0, st, r, M, T, cd, cb,
-                       c2half, bins, k0, k1, n_q, codes);
-    return;
-  }
   hipLaunchKernelGGL(rvq_encode_kernel, dim3(M), dim3(256), 0, st, r, T, cd, cb, c2half, bins, k0, k1, n_q, codes);
 }
 

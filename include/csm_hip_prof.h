@@ -57,8 +57,7 @@ int csm_bench_dec_xsd(csm_engine* e, int iters, float* avg_us, double* bytes);
  * <= 32 bf16 / <= 64 int4 rows, default 1), "dec_xsd_head" (its head in the same launch, default 1),
  * "dec_xsd_sample" (sampled top-k steps: sample_kernel's sampler in the same launch too, default 1),
  * "dec_xsd_stamps" (its per-role clock marks, csm_debug_read "dec_xsd_stamps", default 0),
- * "inject_handoff_error" (test hook).
- * Process-wide lab knobs are environment variables read once (CSM_NT_MASK, CSM_GEMV_XL, CSM_XS_*). */
+ * "inject_handoff_error" (test hook). */
 int csm_set_option(csm_engine* e, const char* key, int value);
 
 /* Launch geometry the streaming matrix-core GEMM (gemm_xs.hip) would use for an (N, K) projection at M

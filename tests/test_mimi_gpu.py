@@ -86,19 +86,22 @@ def test_encode_decode_batch_equals_single():
     assert _rms(y2[1:2], y1) <= 1e-6
 
 
-def test_encode_tiled_rvq_matches_per_row_kernel(monkeypatch):
-    """>= 1024 latent rows take the tiled RVQ kernel (16 rows per block, codebook tiles in LDS); its
-    codes must equal the per-row kernel's (same fmaf chains) and the oracle's."""
-    m, codec, o = _pair("mimi_202407", "mlx", max_batch=24)
-    pcm = np.stack([_pcm(24000 * 4, 40 + b) for b in range(24)])  # 24 x 50 frames = 1200 rows
-    monkeypatch.setenv("CSM_RVQ_TILED", "0")
-    ref_rows = codec.encode(pcm[:, None, :])
-    monkeypatch.setenv("CSM_RVQ_TILED", "1")
-    tiled = codec.encode(pcm[:, None, :])
-    assert tiled.shape == ref_rows.shape and tiled.shape[0] * tiled.shape[2] >= 1024
-    assert np.array_equal(tiled, ref_rows), f"first diff at {np.argwhere(tiled != ref_rows)[:3].tolist()}"
-    ref = o.encode(pcm[[0, 23], None, :])
-    assert np.array_equal(tiled[[0, 23]], ref)
+def test_encode_rvq_gemm_matches_per_row_kernel():
+    """>= 256 latent rows take the distance GEMM (rvq_step_kernel, 64-row tiles: 300 rows leave the last
+    tile ragged at 44), fewer the per-row kernel (rvq_encode_kernel).  Both build every (row, code) dot
+    as one fmaf chain over the dims in order ("the arithmetic of the per-row kernel, so codes
+    and residuals are bit-identical"), so the batched call's codes must equal each clip's own and the
+    oracle's."""
+    m, codec, o = _pair("mimi_202407", "mlx", max_batch=6)
+    pcm = np.stack([_pcm(24000 * 4, 40 + b) for b in range(6)])  # 6 x 50 frames = 300 rows
+    batched = codec.encode(pcm[:, None, :])
+    assert batched.shape[0] * batched.shape[2] == 300
+    for b in range(6):  # 50 rows each: the per-row kernel
+        one = codec.encode(pcm[b: b + 1, None, :])
+        assert np.array_equal(batched[b: b + 1], one), \
+            f"clip {b}: first diff at {np.argwhere(batched[b: b + 1] != one)[:3].tolist()}"
+    ref = o.encode(pcm[[0, 5], None, :])
+    assert np.array_equal(batched[[0, 5]], ref)
 
 
 def test_codes_past_the_codebook_clamp():
