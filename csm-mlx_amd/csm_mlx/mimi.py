@@ -141,6 +141,16 @@ class MimiCodec:
         self._stream_B = None
         return np.concatenate(out, 0)[:, None, :]
 
+    def debug_rows(self) -> np.ndarray:
+        """The engine's row buffer (rows, dimension) as the last call left it (mimi_debug_read "rows"):
+        after ``encode`` the pre-RVQ latent, row = b * Tf + t; after ``decode`` / ``decode_step`` the decoder
+        transformer's output, row = b * n_lat + t.  Of the last ``max_batch`` chunk of a chunked call."""
+        need = ctypes.c_int64(0)
+        _lib.check(_lib.lib().mimi_debug_read(self._h, b"rows", None, 0, ctypes.byref(need)))
+        out = np.zeros((need.value // (4 * self.m.dimension), self.m.dimension), np.float32)
+        _lib.check(_lib.lib().mimi_debug_read(self._h, b"rows", _lib.ptr(out), out.nbytes, ctypes.byref(need)))
+        return out
+
     def reset_state(self, batch_size: int = 1):
         _lib.check(_lib.lib().mimi_reset_state(self._h, batch_size))
         self._stream_B = batch_size

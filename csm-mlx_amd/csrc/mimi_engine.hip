@@ -19,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/csm_hip.h"
+#include "../../include/csm_hip_prof.h"
 #include "engine_util.h"
 #include "mimi_kernels.h"
 
@@ -85,6 +85,7 @@ struct mimi_codec {
   float *W0 = nullptr, *W1 = nullptr, *H = nullptr, *E = nullptr;  // E: ELU of the encoder's current buffer
   float* ks_ws = nullptr;  // split-K scratch of the codec GEMMs (MIMI_KS_WS_FLOATS, mimi_kernels.h)
   float *R = nullptr, *Rh = nullptr, *Rqkv = nullptr, *Rq = nullptr, *Ratt = nullptr, *Rf = nullptr;
+  size_t r_rows = 0;  // rows of R the last call left (mimi_debug_read "rows")
   int* dcodes = nullptr;
   size_t dcodes_n = 0;
   float* dpcm = nullptr;
@@ -690,6 +691,7 @@ int mimi_encode_rows(mimi_codec* m, int B, int N, const float* pcm, const float*
     // split RVQ: semantic and acoustic both quantize the same latent
     launch_conv_to_rows(bufs[cur], B, D, (int)Tf, D * (int)Tf, (int)Tf, 0, m->R, st);
     const int M = B * (int)Tf, cd = d.codebook_dim;
+    m->r_rows = (size_t)M;  // R: the pre-RVQ latent, read only from here on
     grow(m->dcodes, m->dcodes_n, (size_t)B * d.n_q * Tf);
     for (int q = 0; q < 2; ++q) {
       LinParams lp{};
@@ -750,6 +752,7 @@ static void decode_frames(mimi_codec* m, int B, int F, const int32_t* dcodes, in
   launch_conv_to_rows(m->W1, B, D, n_lat, D * n_lat, n_lat, 0, m->R, st);
   run_transformer(m, m->dtr, m->dkc, m->dvc, B, n_lat, m->s_off);
   m->s_off += n_lat;
+  m->r_rows = (size_t)B * n_lat;  // R: the decoder transformer's output, read only from here on
   const int P0 = m->op_pad(m->dec_ops[0]);
   launch_rows_to_conv(m->R, B, D, n_lat, m->W0, D * (P0 + n_lat), P0 + n_lat, P0, st);
   run_decoder_seanet(m, B, n_lat, stream);
@@ -822,6 +825,24 @@ int mimi_decode_step(mimi_codec* m, int B, const int32_t* codes, float* pcm) {
     HIPCHK(hipMemcpyAsync(pcm, src, (size_t)B * n * 4, hipMemcpyDeviceToHost, m->st));
     HIPCHK(hipStreamSynchronize(m->st));
     HIPCHK(hipGetLastError());
+  }
+  CSM_CATCH
+}
+
+int mimi_debug_read(mimi_codec* m, const char* what, void* host, int64_t nbytes, int64_t* needed) {
+  CSM_TRY {
+    if (!m || !what) throw CsmError(CSM_ERR_ARG, "bad mimi_debug_read arguments");
+    const std::string w(what);
+    if (w != "rows") throw CsmError(CSM_ERR_ARG, "unknown codec debug tap " + w);
+    if (!m->R || !m->r_rows) throw CsmError(CSM_ERR_STATE, "no encode / decode call has run yet");
+    HIPCHK(hipSetDevice(m->dev));
+    HIPCHK(hipStreamSynchronize(m->st));
+    const size_t n = m->r_rows * (size_t)m->d.dimension * 4;
+    if (needed) *needed = (int64_t)n;
+    if (host) {
+      if (nbytes < 0 || (size_t)nbytes < n) throw CsmError(CSM_ERR_ARG, "debug buffer too small");
+      HIPCHK(hipMemcpy(host, m->R, n, hipMemcpyDeviceToHost));
+    }
   }
   CSM_CATCH
 }

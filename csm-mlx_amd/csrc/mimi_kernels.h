@@ -63,6 +63,20 @@ struct LinParams {
   float* ks_ws;     // split-K scratch (MIMI_KS_WS_FLOATS) or null
 };
 
+// The host's launch decision for one codec GEMM: which kernel, how many split-K slices, whether the batch
+// is folded into the columns.  launch_conv1d / launch_convtr / launch_linear launch exactly what their
+// mimi_plan_* returns (mimi_lab_plan reports it to the tests).
+enum { MIMI_KERNEL_GEMV = 0, MIMI_KERNEL_GEMM64 = 1, MIMI_KERNEL_WIDE = 2 };
+struct MimiPlan {
+  int kernel;  // MIMI_KERNEL_*
+  int bm;      // wide tile rows (32 / 64 / 128), else 0
+  int ks;      // split-K slices actually launched (1: no split, also without scratch)
+  int fold;    // > 0: the batch folded into the columns, `fold` columns per utterance
+};
+MimiPlan mimi_plan_conv1d(const ConvParams& p);
+MimiPlan mimi_plan_convtr(const ConvTrParams& p);
+MimiPlan mimi_plan_linear(const LinParams& p);
+
 void launch_conv1d(const ConvParams& p, hipStream_t st);
 void launch_convtr(const ConvTrParams& p, hipStream_t st);
 void launch_linear(const LinParams& p, hipStream_t st);

@@ -312,15 +312,28 @@ static void launch_wide(const P& pr, dim3 grid, int ks, float* ws, hipStream_t s
   hipLaunchKernelGGL(splitk_reduce_kernel<P>, dim3(rb), dim3(256), 0, st, pr, ws, ks, Z);
 }
 
-// grid: the 64 x 64 tile grid (its block count also sized the split-K slices, so a wide launch splits
-// exactly as the 64-tile one would: same sums)
+// The host-side choice of every tiled launch, in one place: M x N outputs per grid z (Z of them), KD deep;
+// blocks64 = the 64 x 64 tiles of the batch-folded column space and slab = the outputs of one split-K slice
+// (mimi_splitk's inputs, so a wide launch splits exactly as the 64-tile one would: same sums).
+static MimiPlan mimi_plan_gemm(int M, int N, int Z, int KD, int blocks64, size_t slab, bool wide_ok, bool have_ws,
+                               int fold) {
+  MimiPlan pl{MIMI_KERNEL_GEMM64, 0, have_ws ? mimi_splitk(KD, blocks64, slab) : 1, fold};
+  const int bm = M <= 32 ? 32 : M <= 64 ? 64 : 128;
+  const size_t wblocks = (size_t)((N + 127) / 128) * ((M + bm - 1) / bm) * Z;
+  if (wide_ok && N >= MIMI_WIDE_N && wblocks >= 192) {
+    pl.kernel = MIMI_KERNEL_WIDE;
+    pl.bm = bm;
+  }
+  return pl;
+}
+
+// grid: the 64 x 64 tile grid
 template <class P>
-static void launch_gemm64(const P& pr, dim3 grid, int ks, float* ws, hipStream_t st) {
-  const size_t wblocks = (size_t)((pr.N + 127) / 128) * ((pr.M + (pr.M <= 32 ? 31 : pr.M <= 64 ? 63 : 127)) /
-                                                          (pr.M <= 32 ? 32 : pr.M <= 64 ? 64 : 128)) * grid.z;
-  if (pr.wide_ok() && pr.N >= MIMI_WIDE_N && wblocks >= 192) {
-    if (pr.M <= 32) launch_wide<P, 32>(pr, grid, ks, ws, st);
-    else if (pr.M <= 64) launch_wide<P, 64>(pr, grid, ks, ws, st);
+static void launch_gemm64(const P& pr, dim3 grid, const MimiPlan& pl, float* ws, hipStream_t st) {
+  const int ks = pl.ks;
+  if (pl.kernel == MIMI_KERNEL_WIDE) {
+    if (pl.bm == 32) launch_wide<P, 32>(pr, grid, ks, ws, st);
+    else if (pl.bm == 64) launch_wide<P, 64>(pr, grid, ks, ws, st);
     else launch_wide<P, 128>(pr, grid, ks, ws, st);
     return;
   }
@@ -352,8 +365,6 @@ struct ConvProblem {
   // strided convs (the encoder's downsampling): B staged along the taps -- consecutive kk of one input
   // channel are consecutive input samples
   __device__ bool kcontig() const { return c.stride > 1 && c.dil == 1 && !fold; }
-  // 1-tap convs (K = Cin, memory-bound, mostly with a residual) ran faster on the 64 x 64 tile
-  bool wide_ok() const { return c.k > 1; }
   __device__ bool b4k(int z, int kk0, int t, float (&v)[4]) const {
     const int ci = kk0 / c.k, j = kk0 - ci * c.k;
     const int u = t * c.stride + j - c.pad_l;
@@ -425,12 +436,19 @@ static bool conv_fold_enabled() {
   return v;
 }
 
-void launch_conv1d(const ConvParams& p, hipStream_t st) {
+// 1-tap convs (K = Cin, memory-bound, mostly with a residual) ran faster on the 64 x 64 tile: never wide
+MimiPlan mimi_plan_conv1d(const ConvParams& p) {
   const bool fold = p.Tout < 64 && p.B > 1 && conv_fold_enabled();
-  ConvProblem pr{p, p.Cout, fold ? p.B * p.Tout : p.Tout, fold ? p.Tout : 0};
-  dim3 grid((pr.N + 63) / 64, (p.Cout + 63) / 64, fold ? 1 : p.B);
-  const int ks = mimi_splitk(p.Cin * p.k, ((p.B * p.Tout + 63) / 64) * ((p.Cout + 63) / 64), (size_t)p.B * p.Tout * p.Cout);
-  launch_gemm64(pr, grid, ks, p.ks_ws, st);
+  return mimi_plan_gemm(p.Cout, fold ? p.B * p.Tout : p.Tout, fold ? 1 : p.B, p.Cin * p.k,
+                        ((p.B * p.Tout + 63) / 64) * ((p.Cout + 63) / 64), (size_t)p.B * p.Tout * p.Cout, p.k > 1,
+                        p.ks_ws != nullptr, fold ? p.Tout : 0);
+}
+
+void launch_conv1d(const ConvParams& p, hipStream_t st) {
+  const MimiPlan pl = mimi_plan_conv1d(p);
+  ConvProblem pr{p, p.Cout, pl.fold ? p.B * p.Tout : p.Tout, pl.fold};
+  dim3 grid((pr.N + 63) / 64, (p.Cout + 63) / 64, pl.fold ? 1 : p.B);
+  launch_gemm64(pr, grid, pl, p.ks_ws, st);
 }
 
 // ---------------------------------------------------------------------------- transposed conv (k = 2s)
@@ -447,7 +465,6 @@ struct ConvTrProblem {
   }
   __device__ const float* aptr(int z, int co, int kk) const { return c.wt + ((size_t)(z % c.s) * c.Cout + co) * c.Cin * 2 + kk; }
   __device__ bool kcontig() const { return false; }
-  bool wide_ok() const { return true; }
   __device__ bool b4k(int, int, int, float (&)[4]) const { return false; }
   // inputs i0 .. i0 + 3 of one utterance, all at or after the first: one 4-wide load
   __device__ bool b4(int z, int kk, int i0, float (&v)[4]) const {
@@ -492,13 +509,18 @@ struct ConvTrProblem {
   __device__ void store(int z, int co, int i, float v) const { post(z, co, i, v, pre(z, co, i)); }
 };
 
-void launch_convtr(const ConvTrParams& p, hipStream_t st) {
+MimiPlan mimi_plan_convtr(const ConvTrParams& p) {
   const bool fold = p.n_in < 64 && p.B > 1 && conv_fold_enabled();
-  ConvTrProblem pr{p, p.Cout, fold ? p.B * p.n_in : p.n_in, fold ? p.n_in : 0};
-  dim3 grid((pr.N + 63) / 64, (p.Cout + 63) / 64, fold ? p.s : p.B * p.s);
-  const int ks = mimi_splitk(p.Cin * 2, ((p.B * p.n_in + 63) / 64) * ((p.Cout + 63) / 64) * p.s,
-                             (size_t)p.B * p.n_in * p.s * p.Cout);
-  launch_gemm64(pr, grid, ks, p.ks_ws, st);
+  return mimi_plan_gemm(p.Cout, fold ? p.B * p.n_in : p.n_in, fold ? p.s : p.B * p.s, p.Cin * 2,
+                        ((p.B * p.n_in + 63) / 64) * ((p.Cout + 63) / 64) * p.s, (size_t)p.B * p.n_in * p.s * p.Cout,
+                        true, p.ks_ws != nullptr, fold ? p.n_in : 0);
+}
+
+void launch_convtr(const ConvTrParams& p, hipStream_t st) {
+  const MimiPlan pl = mimi_plan_convtr(p);
+  ConvTrProblem pr{p, p.Cout, pl.fold ? p.B * p.n_in : p.n_in, pl.fold};
+  dim3 grid((pr.N + 63) / 64, (p.Cout + 63) / 64, pl.fold ? p.s : p.B * p.s);
+  launch_gemm64(pr, grid, pl, p.ks_ws, st);
 }
 
 // ---------------------------------------------------------------------------- linear (rows x W^T)
@@ -511,7 +533,6 @@ struct LinProblem {
   __device__ float b(int, int kk, int m) const { return c.x[(size_t)m * c.xs + kk]; }
   __device__ const float* aptr(int, int n, int kk) const { return c.W + (size_t)n * c.K + kk; }
   __device__ bool kcontig() const { return true; }
-  bool wide_ok() const { return true; }
   __device__ bool b4k(int, int kk0, int m, float (&v)[4]) const {
     ld4(c.x + (size_t)m * c.xs + kk0, v);
     return true;
@@ -561,9 +582,17 @@ struct LinProblem {
 // GEMV, which re-reads the weights for every 4-row pass (profiles/r04_prof_config3_per_frame.txt).
 constexpr int MIMI_GEMV_ROWS = 16;  // the largest row count on the GEMV
 
-void launch_linear(const LinParams& p, hipStream_t st) {
+MimiPlan mimi_plan_linear(const LinParams& p) {
   if (!p.conv_T && p.M <= MIMI_GEMV_ROWS && p.N % 8 == 0 && p.K % 8 == 0 &&
-      p.N % gemv_rows_per_block(p.N, p.K, p.M) == 0 && gemv_rows_per_block(p.N, p.K, p.M) % 2 == 0) {
+      p.N % gemv_rows_per_block(p.N, p.K, p.M) == 0 && gemv_rows_per_block(p.N, p.K, p.M) % 2 == 0)
+    return MimiPlan{MIMI_KERNEL_GEMV, 0, 1, 0};
+  const int blocks = ((p.M + 63) / 64) * ((p.N + 63) / 64);
+  return mimi_plan_gemm(p.N, p.M, 1, p.K, blocks, (size_t)p.M * p.N, true, p.ks_ws != nullptr, 0);
+}
+
+void launch_linear(const LinParams& p, hipStream_t st) {
+  const MimiPlan pl = mimi_plan_linear(p);
+  if (pl.kernel == MIMI_KERNEL_GEMV) {
     GemvParams g{};
     g.W = p.W; g.N = p.N; g.K = p.K; g.x = p.x; g.xs = p.xs; g.M = p.M; g.out = p.out; g.os = p.os;
     g.scale = p.scale; g.gelu_erf = p.gelu_erf;
@@ -572,8 +601,7 @@ void launch_linear(const LinParams& p, hipStream_t st) {
   }
   LinProblem pr{p, p.N, p.M};
   dim3 grid((p.M + 63) / 64, (p.N + 63) / 64, 1);
-  const int ks = mimi_splitk(p.K, (int)(grid.x * grid.y), (size_t)p.M * p.N);
-  launch_gemm64(pr, grid, ks, p.ks_ws, st);
+  launch_gemm64(pr, grid, pl, p.ks_ws, st);
 }
 
 // ============================================================================ LayerNorm rows

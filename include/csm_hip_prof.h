@@ -76,6 +76,43 @@ int csm_q4_gemv_shape(int N, int K, int* out);
  * (tests/test_gemm_kernel_gpu.py checks every nibble value at every position).  Returns CSM_OK or an error. */
 int csm_q4_expand(const uint32_t* words, int n, uint32_t* out);
 
+/* ---- Mimi codec lab door (csrc/mimi_lab.hip): one codec kernel launch on host arrays, no codec handle.
+ * Each entry allocates on the current device, uploads, launches on a stream of its own with its own
+ * split-K scratch, downloads and frees.  Output arrays are in / out: their content is uploaded first (a
+ * sentinel, or the values an accumulating store adds onto) and the whole array comes back, so a store
+ * outside the addressed region shows.  A geometry that does not fit its arrays (sizes in elements) is
+ * CSM_ERR_ARG and nothing is launched.  The geometry arrays hold the parameter blocks' fields
+ * (csrc/mimi_kernels.h) in this order:
+ *   conv1d (21): Cin, Tin, x_bstride, x_off, x_cstride, Cout, k, stride, dil, pad_l, replicate, elu_in,
+ *                Tout, y_bstride, y_cstride, y_off, r_bstride, r_cstride, r_off, B, elu_out
+ *   convtr (14): Cin, Tin, x_bstride, x_cstride, x_off, Cout, s, elu_in, t_in0, n_in, y_bstride,
+ *                y_cstride, y_off, B
+ *   linear (10): M, K, xs, N, os, epi (0 store, 1 add, 4 GELU), gelu_erf, conv_T, conv_bstride, accumulate */
+
+/* What the launcher would run for a geometry (op 0 conv1d, 1 convtr, 2 linear), from the function the
+ * launchers themselves call: out[4] = {kernel (0 decode GEMV, 1 64 x 64 tile, 2 wide BM x 128 tile), BM of
+ * the wide tile (32 / 64 / 128, else 0), split-K slices, fold (columns per utterance of a batch-folded
+ * launch, else 0)}.  Host-only. */
+int mimi_lab_plan(int op, const int* geo, int n_geo, int* out);
+/* bias [Cout], resid (layout r_*), y2 (layout of y) optional (NULL); w [Cout][Cin][k]. */
+int mimi_lab_conv1d(const int* geo, int n_geo, const float* x, int64_t x_n, const float* w, int64_t w_n,
+                    const float* bias, const float* resid, int64_t r_n, float* y, float* y2, int64_t y_n);
+/* wt [s][Cout][Cin][2] (phase-major, tap e = 0 then 1); bias optional. */
+int mimi_lab_convtr(const int* geo, int n_geo, const float* x, int64_t x_n, const float* wt, int64_t w_n,
+                    const float* bias, float* y, int64_t y_n);
+/* W [N][K]; scale [N] optional (epi add). */
+int mimi_lab_linear(const int* geo, int n_geo, const float* x, int64_t x_n, const float* W, int64_t w_n,
+                    const float* scale, float* out, int64_t out_n);
+/* RVQ encode of rows r [M][cd] (in / out: the final residual) over codebooks [k0, k1) of cb [n_q][bins][cd]
+ * with c2half [n_q][bins]; codes [M / T][n_q][T] in / out.  gemm = 0: the block-per-row kernel, 1: the
+ * distance GEMM (cd % 32 == 0, cd <= 256, bins % 256 == 0). */
+int mimi_lab_rvq_encode(int gemm, int M, int T, int cd, int bins, int n_q, int k0, int k1, const float* cb,
+                        const float* c2half, float* r, int32_t* codes);
+/* Inspection tap of a codec: "rows" = the engine's row buffer [rows][dimension] as the last call left it:
+ * after mimi_encode* the pre-RVQ latent [B * Tf][D], after mimi_decode / mimi_decode_step the decoder
+ * transformer's output [B * n_lat][D].  *needed = its bytes; host NULL: size query only. */
+int mimi_debug_read(mimi_codec* m, const char* what, void* host, int64_t nbytes, int64_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

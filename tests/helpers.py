@@ -252,6 +252,48 @@ def f64_reference(args, weights, variant, prompts, codes):
     return t64, {tap: float(e.max()) for tap, e in tap_errors(t32, t64).items()}
 
 
+# ----------------------------------------------------------------------------- the Mimi codec against float64
+# bar = MIMI_BAR_MARGIN x e32 on every frame of every utterance (tests/test_mimi_f64_gpu.py).  The margin starts
+# from the CSM taps' and is capped the same way (tests/test_mimi_f64_cpu.py asserts it): it may not exceed half
+# the smallest defect that the bar has to catch, in units of e32.
+MIMI_BAR_MARGIN = BAR_MARGIN
+
+
+def mimi_pair(name, mode):
+    """(MimiArgs, synthetic weights, float32 oracle, float64 oracle) of a codec config, memoised."""
+    key = ("mimi", name, mode)
+    if key not in _ORACLES:
+        from csm_mlx.config import MIMI_CONFIGURATION
+        from csm_mlx.weights import synthetic_mimi_weights
+        from oracle.mimi_oracle import OracleMimi
+        m = dataclasses.replace(MIMI_CONFIGURATION[name], attn_mode=mode)
+        w = synthetic_mimi_weights(m)
+        _ORACLES[key] = (m, w, OracleMimi(m, w), OracleMimi(m, w, dtype=np.float64))
+    return _ORACLES[key]
+
+
+def mimi_errors(got, ref64, frame=None):
+    """got / ref64 (B, ..., n): a waveform (B, 1, F * frame), or rows (B, T, D) with frame None.  Per
+    utterance and per frame of ``frame`` samples (per row): max |got - float64| / the utterance's largest
+    |float64 value|.  Returns (B, F) or (B, T)."""
+    r = np.asarray(ref64, np.float64)
+    g = np.asarray(got, np.float64)
+    B = r.shape[0]
+    assert g.shape == r.shape, (g.shape, r.shape)
+    if frame is not None:
+        g, r = g.reshape(B, -1, frame), r.reshape(B, -1, frame)
+    return np.abs(g - r).max(-1) / np.abs(r).reshape(B, -1).max(-1)[:, None]
+
+
+def mimi_pcm_clip(n, seed=0, amp=0.1):
+    """The encode tests' clip: three seeded sines plus noise."""
+    t = np.arange(n) / 24000.0
+    rng = np.random.default_rng(seed)
+    f = rng.uniform(100, 400, 3)
+    x = amp * sum(np.sin(2 * np.pi * fi * t + rng.uniform(0, 6.28)) for fi in f) + rng.normal(0, 0.01, n)
+    return x.astype(np.float32)
+
+
 # ----------------------------------------------------------------------------- one projection against float64
 def cut16(a):
     """hi + mid of the matrix-core paths' activation split (csrc/xs.h split3): two truncations to bf16, the
