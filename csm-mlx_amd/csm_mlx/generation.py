@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from .models import CSM
-from .sampling import HostSampler, Sampler
+from .sampling import C0_WINDOW_MAX, HostSampler, LogitBias, RepetitionPenalty, Sampler
 from .segment import Segment
 from .tokenizers import decode_audio, get_audio_tokenizer, tokenize_segment, tokenize_text_segment
 
@@ -39,6 +39,22 @@ def _resolve_sampler(temperature: float, sampler, top_k: int = 0):
             return HostSampler(sampler)
         raise TypeError(f"sampler must be a csm_mlx.sampling.Sampler or a callable, got {type(sampler).__name__}")
     return Sampler(float(temperature), int(top_k))
+
+
+def device_processors(logits_processors, sampler) -> Optional[Tuple[Optional[LogitBias], Optional[RepetitionPenalty]]]:
+    """The (bias, penalty) pair when ``logits_processors`` can run inside the frame on the GPU
+    (csm_set_c0_processors), else None: the list must be at most one ``LogitBias`` followed by at most
+    one ``RepetitionPenalty`` and nothing else (two biases are not merged: (l + b1) + b2 is not
+    l + (b1 + b2) in float32), the penalty's window within the device cap, and the sampler not a host
+    callable.  Every other list pauses the frame for the host, as an empty one runs the plain frame."""
+    procs = list(logits_processors or ())
+    if not procs or isinstance(sampler, HostSampler):
+        return None
+    bias = procs.pop(0) if type(procs[0]) is LogitBias else None
+    pen = procs.pop(0) if procs and type(procs[0]) is RepetitionPenalty else None
+    if procs or (pen is not None and not 1 <= pen.context_size <= C0_WINDOW_MAX):
+        return None      # (context_size 0 is mlx_lm's tokens[-0:], the whole history: the host's)
+    return bias, pen
 
 
 def _seed_list(seed, B: int) -> np.ndarray:
@@ -63,7 +79,9 @@ class FrameCache:
     instead of silently reading the new state (the reference's KVCache lists are independent
     objects; here the caches live in the engine)."""
 
-    def __init__(self, model: CSM, batch_size: int, sampler: Sampler, seeds=None):
+    def __init__(self, model: CSM, batch_size: int, sampler: Sampler, seeds=None, processors=None):
+        """processors: a ``device_processors`` pair (bias, penalty) the engine applies to the c0 logits
+        inside every frame of this batch."""
         self.model = model
         self.B = batch_size
         self.sampler = sampler
@@ -73,6 +91,15 @@ class FrameCache:
         if not sampler.greedy and sampler.filtered:
             _lib.check(self.L.csm_set_sampler_filters(model.engine, sampler.top_p, sampler.min_p,
                                                       sampler.min_tokens_to_keep))
+        if processors is not None:
+            bias, pen = processors
+            idx = np.asarray(bias.indices if bias else (), np.int64)
+            val = np.ascontiguousarray(bias.values if bias else (), np.float32)
+            if idx.size and (idx.min() < 0 or idx.max() >= model.n_audio_vocab):   # no silent clamp
+                raise ValueError(f"logit_bias index outside [0, {model.n_audio_vocab}): {idx.min()} .. {idx.max()}")
+            idx = np.ascontiguousarray(idx, np.int32)
+            _lib.check(self.L.csm_set_c0_processors(model.engine, len(idx), _lib.ptr(idx), _lib.ptr(val),
+                                                    pen.penalty if pen else 0.0, pen.context_size if pen else 0))
         model._generation = getattr(model, "_generation", 0) + 1
         self._gen = model._generation
         self.frames = 0
@@ -271,8 +298,10 @@ def _mark(timings: Optional[dict], key: str, t0: float, model: Optional[CSM] = N
 def generate_codes_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], max_audio_frames: int, *,
                          sampler: Sampler, seeds=None, chunk: int = 8,
                          logits_processors: Optional[List[Callable]] = None, timings: Optional[dict] = None):
-    """Run the frame loop for B prompts.  Returns (hist [F,B,K], n_frames [B], cache).  With
-    ``logits_processors`` every frame pauses after codebook0_head for them (generation.py:44-49).
+    """Run the frame loop for B prompts.  Returns (hist [F,B,K], n_frames [B], cache).
+    ``logits_processors`` from ``make_logits_processors`` run on the GPU inside the frame
+    (``device_processors``); with any other list every frame pauses after codebook0_head for the host
+    (generation.py:44-49).
     ``timings`` (optional dict): wall seconds of the prompt prefill and of the frames are added to
     its "prefill" / "frames" entries (the engine is synchronized at each boundary)."""
     import time
@@ -280,7 +309,10 @@ def generate_codes_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndar
     for t, _ in prompts:
         _check_window(model, t.shape[0], max_audio_frames)
     t0 = time.perf_counter()
-    cache = FrameCache(model, B, sampler, seeds)
+    on_device = device_processors(logits_processors, sampler)
+    if on_device is not None:
+        logits_processors = None
+    cache = FrameCache(model, B, sampler, seeds, on_device)
     if B > 1:   # every prompt's rows through one pass of each projection (weights streamed once)
         cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(prompts)])
     else:
@@ -346,14 +378,15 @@ def generate(model: CSM, text, speaker: int, context: List[Segment], max_audio_l
 
 def generate_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], max_audio_length_ms: float = 10_000,
                    *, temperature: float = 0.0, top_k: int = 0, sampler=None, seeds=None, decode: bool = True,
-                   with_codes: bool = False, timings: Optional[dict] = None):
+                   with_codes: bool = False, timings: Optional[dict] = None,
+                   logits_processors: Optional[List[Callable]] = None):
     """Batched extension: B prompts (tokens, mask) -> list of waveforms (or codes if decode=False;
     (codes, waveforms) with ``with_codes``).  ``timings``: per-phase wall seconds (prefill, frames,
     decode) added to the dict."""
     import time
     smp = _resolve_sampler(temperature, sampler, top_k)
     hist, n_frames, _ = generate_codes_batch(model, prompts, int(max_audio_length_ms / 80), sampler=smp, seeds=seeds,
-                                             timings=timings)
+                                             timings=timings, logits_processors=logits_processors)
     codes = [hist[: n_frames[b], b] for b in range(len(prompts))]
     if not decode:
         return codes
@@ -393,7 +426,7 @@ def _host_sampled_frames(cache: "FrameCache", codec, max_audio_frames: int, samp
 
 
 def _processed_frames(cache: "FrameCache", codec, max_audio_frames: int, processors):
-    """The streaming loop with host logits processors: each frame pauses after codebook0_head, so
+    """The streaming loop with host logits processors (lists ``device_processors`` turns down): each frame pauses after codebook0_head, so
     there is nothing to overlap; EOS is tested before the frame is decoded (generation.py:237-251)."""
     c0_history: list = []
     for _ in range(max_audio_frames):
@@ -404,7 +437,8 @@ def _processed_frames(cache: "FrameCache", codec, max_audio_frames: int, process
 
 def stream_generate_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]],
                           max_audio_length_ms: float = 10_000, *, temperature: float = 0.8, top_k: int = 0,
-                          sampler=None, seeds=None) -> Generator[Tuple[np.ndarray, np.ndarray], None, None]:
+                          sampler=None, seeds=None, logits_processors: Optional[List[Callable]] = None
+                          ) -> Generator[Tuple[np.ndarray, np.ndarray], None, None]:
     """Batched extension of ``stream_generate`` (generation.py:181-258): per frame yields
     (pcm (B, 1920) float32 from the codec's streaming ``decode_step``, done (B,) bool).  An
     utterance's rows after its EOS frame are not audio (its ``done`` flag is set)."""
@@ -414,12 +448,17 @@ def stream_generate_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.nda
     smp = _resolve_sampler(temperature, sampler, top_k)
     B = len(prompts)
     codec = get_audio_tokenizer(model.n_audio_codebooks)
-    cache = FrameCache(model, B, smp, seeds)
+    on_device = device_processors(logits_processors, smp)
+    if on_device is not None:
+        logits_processors = None
+    cache = FrameCache(model, B, smp, seeds, on_device)
     cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(prompts)])
     codec.reset_state(B)
     try:
         if isinstance(smp, HostSampler):
-            yield from _host_sampled_frames(cache, codec, max_audio_frames, smp, None)
+            yield from _host_sampled_frames(cache, codec, max_audio_frames, smp, logits_processors)
+        elif logits_processors:
+            yield from _processed_frames(cache, codec, max_audio_frames, logits_processors)
         else:
             yield from _overlapped_frames(cache, codec, max_audio_frames)
     finally:
@@ -438,7 +477,10 @@ def stream_generate(model: CSM, text, speaker: int, context: List[Segment], max_
     _check_window(model, t.shape[0], max_audio_frames)
     smp = _resolve_sampler(temperature, sampler)
     codec = get_audio_tokenizer(model.n_audio_codebooks)
-    cache = FrameCache(model, 1, smp, seed)
+    on_device = device_processors(logits_processors, smp)
+    if on_device is not None:
+        logits_processors = None
+    cache = FrameCache(model, 1, smp, seed, on_device)
     cache.prefill(0, t, m)
     codec.reset_state(1)
     try:

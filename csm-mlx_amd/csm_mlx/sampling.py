@@ -9,6 +9,11 @@ driven by a counter-based splitmix64 stream keyed by (seed, frame*K + codebook,
 vocab id).  The filter chain's restatement is oracle/csm_oracle.py
 ``filter_keep``; the GPU side is ``sample_filtered_kernel`` (csm_kernels.hip).
 
+``make_logits_processors`` is the other half of the mlx_lm pair the reference README imports
+(README.md:96, :120-122): ``LogitBias`` / ``RepetitionPenalty`` descriptors of the two standard c0
+processors.  The engine runs them inside the frame (csm_set_c0_processors); each is also a numpy
+callable ``(tokens, logits) -> logits`` for the host paths and the oracle.
+
 An arbitrary callable (``sampler=fn``, as the reference CLI passes mlx_lm's sampler) is honoured too,
 and so is ``make_sampler(xtc_probability=...)`` (XTC has no GPU counterpart: the chain runs there),
 on the host: ``HostSampler`` wraps it, and every frame then hands each codebook's logits (B, V) to
@@ -18,6 +23,10 @@ so a compatibility path, not the fast one).
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Tuple
+
+# the longest repetition window the engine applies inside the frame (csrc/csm_kernels.h C0_WINDOW_MAX)
+C0_WINDOW_MAX = 256
 
 
 @dataclass(frozen=True)
@@ -138,3 +147,59 @@ class HostSampler:
             x = x - (m + np.log(np.exp(x - m).sum(axis=-1, keepdims=True)))
         return np.asarray(self.fn(x)).reshape(x.shape[0]).astype(np.int32)
 
+
+
+@dataclass(frozen=True)
+class LogitBias:
+    """mlx_lm's logit_bias processor on the c0 logits: ``logits[:, indices] += values`` in float32.
+    A descriptor the engine applies inside the frame, and a callable (tokens, logits (B, V)) -> logits."""
+    indices: Tuple[int, ...]
+    values: Tuple[float, ...]
+
+    def __call__(self, tokens, logits):
+        import numpy as np
+        out = np.array(logits, np.float32, copy=True)
+        out[..., list(self.indices)] += np.asarray(self.values, np.float32)
+        return out
+
+
+@dataclass(frozen=True)
+class RepetitionPenalty:
+    """mlx_lm's repetition penalty on the c0 logits: for every distinct code t among an utterance's last
+    ``context_size`` c0 codes (``tokens[-context_size:]``; nothing when the history is empty),
+    ``logits[t] * penalty`` when negative, else ``logits[t] / penalty``, in float32 -- each code once,
+    however often it occurs (the reference's fancy-index assignment reads every value, then writes).
+    ``tokens`` is the stacked c0 history (F, B, 1): row b of the logits sees utterance b's own codes."""
+    penalty: float
+    context_size: int = 20
+
+    def __call__(self, tokens, logits):
+        import numpy as np
+        out = np.array(logits, np.float32, copy=True)
+        tokens = np.asarray(tokens)
+        if tokens.size == 0:
+            return out
+        rows = out.reshape(-1, out.shape[-1])
+        window = tokens.reshape(tokens.shape[0], -1)[-self.context_size:]         # (n, B)
+        pen = np.float32(self.penalty)
+        for b in range(rows.shape[0]):
+            t = np.unique(window[:, b if window.shape[1] > 1 else 0])
+            sel = rows[b, t]
+            rows[b, t] = np.where(sel < 0, sel * pen, sel / pen)
+        return out
+
+
+def make_logits_processors(logit_bias=None, repetition_penalty=None, repetition_context_size: int = 20):
+    """mlx_lm.sample_utils.make_logits_processors (reference README.md:96, :120-122) as a list of
+    descriptors: a ``LogitBias`` when ``logit_bias`` ({index: value}) is non-empty, then a
+    ``RepetitionPenalty`` when ``repetition_penalty`` is non-zero.  The bias runs first."""
+    out = []
+    if logit_bias:
+        idx = tuple(int(i) for i in logit_bias.keys())
+        out.append(LogitBias(idx, tuple(float(v) for v in logit_bias.values())))
+    if repetition_penalty and repetition_penalty != 0.0:
+        if isinstance(repetition_penalty, bool) or not isinstance(repetition_penalty, (int, float)) \
+                or repetition_penalty < 0:
+            raise ValueError("repetition_penalty must be a non-negative float")
+        out.append(RepetitionPenalty(float(repetition_penalty), int(repetition_context_size)))
+    return out

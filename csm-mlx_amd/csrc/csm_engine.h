@@ -161,7 +161,15 @@ struct csm_engine {
   // mlx_lm filter chain beyond top-k (csm_set_sampler_filters; reset by csm_begin)
   int use_top_p = 0, use_min_p = 0, min_keep = 1;
   float top_p_cut = 0.f, log_min_p = 0.f;
-  int filters_id = 0, g_filters = -1;  // graphs capture the filter parameters by value
+  int filters_id = 0, g_filters = -1;  // graphs capture the filter (and c0 processor) parameters by value
+  // mlx_lm make_logits_processors on the c0 logits, run inside the frame (csm_set_c0_processors; reset by
+  // csm_begin): a dense bias vector [Vpad] (zero where unset) and the repetition penalty over the last
+  // c0_context c0 codes of each utterance's history
+  float* c0_bias = nullptr;
+  bool c0_bias_on = false;
+  float c0_penalty = 0.f;
+  int c0_context = 0;
+  bool c0_processors() const { return c0_bias_on || c0_penalty > 0.f; }
   int frames_run = 0;
   bool need_body = false;
   std::vector<int> prompt_len;

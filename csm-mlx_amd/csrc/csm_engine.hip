@@ -262,6 +262,7 @@ void enqueue_dec_frame_only(csm_engine* e, hipStream_t st) {
   a.V = e->V; a.VP = e->Vpad; a.K = e->K; a.codes = e->codes; a.c0_logits = e->c0_logits; a.ci_logits = e->ci_logits;
   // (wnt / hnt stay zero: no kernel reads them any more)
   a.temperature = e->temperature; a.top_k = e->top_k; a.seeds = e->seeds; a.frame_ctr = e->frame_ctr;
+  a.c0_bias = e->c0_bias_on ? e->c0_bias : nullptr; a.hist = e->hist; a.c0_penalty = e->c0_penalty; a.c0_context = e->c0_context;
   launch_dec_frame(a, st, e->wdt == WDT_Q4);
 }
 
@@ -411,7 +412,9 @@ void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piec
   const int B = e->B, K = e->K, D = e->D, Dd = e->Dd, V = e->V, Vp = e->Vpad;
   const bool host_codes = phase == HeadPhase::Forced || phase == HeadPhase::HostPiece;  // fed forward from e->force
   const bool greedy = e->temperature <= 0.f && !host_codes;
-  const bool c0_sampled = !greedy || phase == HeadPhase::FromHostC0;  // c0 published by sample_kernel as a single partial
+  // the frame's own logits processors (csm_set_c0_processors) transform the stored c0 logits before c0 is picked
+  const bool c0_proc = phase == HeadPhase::Frame && e->c0_processors();
+  const bool c0_sampled = !greedy || phase == HeadPhase::FromHostC0 || c0_proc;  // c0 published by sample_kernel as a single partial
   // sampled frames (top-k only): the persistent step's launch can run the sampler too
   const bool fuse_sample = !greedy && (phase == HeadPhase::Frame || phase == HeadPhase::FromHostC0) && !e->use_top_p && !e->use_min_p;
   const int n0 = head_blocks(Vp, D, B, e->wdt);        // c0-head blocks (partials per row)
@@ -428,8 +431,14 @@ void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piec
   g.W = e->c0_head; g.N = Vp; g.K = D; g.x = e->h_last; g.xs = D; g.M = B; g.out = e->c0_logits; g.os = Vp;
   g.part = part(0); g.part_stride = e->part_stride; g.n_valid = V;
   if (phase != HeadPhase::FromHostC0 && phase != HeadPhase::HostPiece)
-    launch_gemv(g, e->wdt, (greedy && phase == HeadPhase::Frame) ? EPI_ARGMAX : EPI_STORE, 0, st);
+    launch_gemv(g, e->wdt, (greedy && phase == HeadPhase::Frame && !c0_proc) ? EPI_ARGMAX : EPI_STORE, 0, st);
   if (phase == HeadPhase::C0Logits) return;
+  if (c0_proc) {
+    C0ProcessParams cp{};
+    cp.logits = e->c0_logits; cp.ls = Vp; cp.V = V; cp.bias = e->c0_bias_on ? e->c0_bias : nullptr; cp.penalty = e->c0_penalty;
+    cp.context = e->c0_context; cp.hist = e->hist; cp.B = B; cp.K = K; cp.frame_ctr = e->frame_ctr;
+    launch_c0_process(cp, st);
+  }
   const bool pieces = phase == HeadPhase::HostPiece;
   const int cb_first = pieces ? piece - 1 : 0;  // the code fed forward before the first step below
   if (c0_sampled) {

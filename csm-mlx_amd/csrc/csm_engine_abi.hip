@@ -57,6 +57,9 @@ int csm_begin(csm_engine* e, int B, const uint64_t* seeds, float temperature, in
     e->use_top_p = e->use_min_p = 0;
     e->min_keep = 1;
     e->top_p_cut = e->log_min_p = 0.f;
+    e->c0_bias_on = false;
+    e->c0_penalty = 0.f;
+    e->c0_context = 0;
     ++e->filters_id;
     e->frames_run = 0;
     e->need_body = false;
@@ -87,6 +90,34 @@ int csm_set_sampler_filters(csm_engine* e, double top_p, double min_p, int min_t
     e->log_min_p = e->use_min_p ? (float)std::log(min_p) : 0.f;
     e->min_keep = min_tokens_to_keep;
     ++e->filters_id;
+  }
+  CSM_CATCH
+}
+
+int csm_set_c0_processors(csm_engine* e, int n_bias, const int32_t* bias_idx, const float* bias_val, float repetition_penalty,
+                          int repetition_context_size) {
+  CSM_TRY {
+    if (!e) throw CsmError(CSM_ERR_ARG, "null engine");
+    if (e->frames_run > 0 || e->c0_pending) throw CsmError(CSM_ERR_STATE, "set the c0 processors before the first frame");
+    if (n_bias < 0 || (n_bias > 0 && (!bias_idx || !bias_val))) throw CsmError(CSM_ERR_ARG, "bad logit_bias arguments");
+    for (int i = 0; i < n_bias; ++i)
+      if (bias_idx[i] < 0 || bias_idx[i] >= e->V)
+        throw CsmError(CSM_ERR_ARG, "logit_bias index " + std::to_string(bias_idx[i]) + " outside [0, " + std::to_string(e->V) + ")");
+    if (!(repetition_penalty >= 0.f)) throw CsmError(CSM_ERR_ARG, "repetition_penalty must be >= 0");
+    if (repetition_context_size < 0 || repetition_context_size > C0_WINDOW_MAX)
+      throw CsmError(CSM_ERR_ARG, "repetition_context_size must lie in [0, " + std::to_string(C0_WINDOW_MAX) + "]");
+    HIPCHK(hipSetDevice(e->dev));
+    if (n_bias > 0) {
+      if (!e->c0_bias) e->c0_bias = (float*)e->alloc((size_t)e->Vpad * 4);
+      std::vector<float> dense(e->Vpad, 0.f);
+      for (int i = 0; i < n_bias; ++i) dense[bias_idx[i]] = bias_val[i];  // (a repeated index: the last value)
+      HIPCHK(hipMemcpyAsync(e->c0_bias, dense.data(), dense.size() * 4, hipMemcpyHostToDevice, e->st));
+      HIPCHK(hipStreamSynchronize(e->st));
+    }
+    e->c0_bias_on = n_bias > 0;
+    e->c0_penalty = repetition_penalty;
+    e->c0_context = repetition_penalty > 0.f ? repetition_context_size : 0;
+    ++e->filters_id;  // the frame graphs hold these by value: re-capture
   }
   CSM_CATCH
 }

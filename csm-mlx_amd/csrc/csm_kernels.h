@@ -264,6 +264,22 @@ struct SampleParams {
   float top_p_cut, log_min_p;
 };
 
+// mlx_lm make_logits_processors on the c0 logits, run inside the frame (csm_set_c0_processors; c0_process.h
+// holds the per-logit rule).  The repetition window is the c0 codes of an utterance's last
+// min(frame, context) frames, read from the code history; C0_WINDOW_MAX is the device cap of context.
+constexpr int C0_WINDOW_MAX = 256;
+struct C0ProcessParams {
+  float* logits;       // [B][ls], transformed in place
+  int ls, V;
+  const float* bias;   // [ls] dense, zero where unset; null: no bias
+  float penalty;       // 0: no repetition penalty
+  int context;
+  const int* hist;     // [F_cap][B][K]
+  int B, K;
+  const int* frame_ctr;
+};
+void launch_c0_process(const C0ProcessParams& p, hipStream_t st);
+
 struct AdvanceParams {
   int* codes;
   int* hist;      // [F_cap][B][K]
@@ -415,6 +431,12 @@ struct DecFrameArgs {
   int top_k;
   const uint64_t* seeds;                 // [1] utterance 0's sampling seed
   const int* frame_ctr;                  // frame index (the sampler's counter)
+  // logits processors on c0 (csm_set_c0_processors; c0_process.h): applied to codebook0_head's rows before
+  // the tap and the hand-off
+  const float* c0_bias;                  // [VP] dense bias; null: none
+  const int* hist;                       // [F][1][K] code history of utterance 0 (the repetition window)
+  float c0_penalty;                      // 0: no repetition penalty
+  int c0_context;                        // window length, <= C0_WINDOW_MAX
 };
 constexpr int DEC_FRAME_STAMPS = 1024;
 size_t dec_frame_gbuf_bytes();

@@ -12,6 +12,7 @@
 //   advance        EOS flag (generation.py:151), code history, frame counter
 // Weights are streamed straight to VGPRs with 16-B loads (GEMV / M <= 16 regime: no LDS
 // round trip); x rows are tiny and served from L1/L2.
+#include "c0_process.h"
 #include "csm_kernels.h"
 #include "engine_util.h"
 #include "xs.h"
@@ -1374,6 +1375,21 @@ __global__ void advance_kernel(AdvanceParams p) {
   if (threadIdx.x == 0) p.frame_ctr[0] = f + 1;
 }
 
+// ============================================================================ c0 logits processors
+// mlx_lm make_logits_processors on the c0 logits of the launch path, in place between the c0 head's
+// GEMV and the sampler: one block per utterance, its repetition window (c0 of the last min(frame, context)
+// frames, from the code history) staged in LDS, every thread logits v, v + 256, ... through the shared
+// per-logit rule (c0_process.h).
+__global__ __launch_bounds__(256) void c0_process_kernel(C0ProcessParams p) {
+  __shared__ int win[C0_WINDOW_MAX];
+  const int b = blockIdx.x, f = p.frame_ctr[0];
+  const int n = c0_window_n(f, p.context, p.penalty);
+  for (int j = threadIdx.x; j < n; j += 256) win[j] = c0_window_code(p.hist, f, j, b, p.B, p.K);
+  __syncthreads();
+  float* lg = p.logits + (size_t)b * p.ls;
+  for (int v = threadIdx.x; v < p.V; v += 256) lg[v] = c0_processed(lg[v], v, p.bias, win, n, p.penalty);
+}
+
 // ============================================================================ launchers
 // tiling choice (G threads per row group, RPT rows per thread)
 
@@ -1582,6 +1598,11 @@ __global__ __launch_bounds__(256) void forced_ce_kernel(const float* c0, const f
 void launch_forced_ce(const float* c0, const float* ci, const int* forced, float* out, int B, int K, int V, int Vp,
                       hipStream_t st) {
   hipLaunchKernelGGL(forced_ce_kernel, dim3(B * K), dim3(256), 0, st, c0, ci, forced, out, B, K, V, Vp);
+}
+
+void launch_c0_process(const C0ProcessParams& p, hipStream_t st) {
+  if (p.context < 0 || p.context > C0_WINDOW_MAX) throw CsmError(CSM_ERR_ARG, "c0 processors: window beyond C0_WINDOW_MAX");
+  hipLaunchKernelGGL(c0_process_kernel, dim3(p.B), dim3(256), 0, st, p);
 }
 
 void launch_advance(const AdvanceParams& p, hipStream_t st) {

@@ -34,6 +34,7 @@
 // max subtraction, reductions in fixed orders (deterministic run to run).
 #include <type_traits>
 
+#include "c0_process.h"
 #include "csm_kernels.h"
 #include "handoff.h"
 
@@ -112,6 +113,9 @@ struct Lds {
   float xh[MAXM][D / 32];
   alignas(16) float aq[MAXM][D / 32][36];
   float ah[MAXM][D / 32];
+  // logits processors on c0 (c0_stage): the repetition window and the bias of this WG's head rows
+  int c0win[C0_WINDOW_MAX];
+  float c0b[16];           // rows 8w .. 8w + 7, then row 2048 + w
 };
 
 }  // namespace
@@ -821,10 +825,12 @@ __device__ __forceinline__ unsigned long long dkey(double d) {
 }
 
 // Head rows of this WG on row xn[0] (K = 1024 or 2048) -> arg-max key -> E6 granules (hi, lo words)
+// C0: codebook0_head, whose rows the logits processors (DecFrameArgs::c0_bias / c0_penalty) transform first
+template <bool C0 = false>
 __device__ __forceinline__ void head_publish(Ctx& c, float s, float t, int n_valid, float* logits, int cb);
 // PAD: the input row is the int4 kernel's padded xq[xm] (element k at q4p(k): an 8-element chunk stays
 // contiguous), else L.xn[xm]
-template <int KH, bool PAD = false>
+template <int KH, bool PAD = false, bool C0 = false>
 __device__ __forceinline__ void phase_head(Ctx& c, const bf16_t* W, int n_valid, const u32x4_t (&wa)[KH / 512],
                                            const u32x4_t (&wx)[KH / 512], float* logits, int cb, int xm = 0, float rs = 1.f) {
   constexpr int CPL = KH / 512;  // chunks per lane
@@ -844,13 +850,23 @@ __device__ __forceinline__ void phase_head(Ctx& c, const bf16_t* W, int n_valid,
     for (int i = 0; i < CPL; ++i) t += dot8(wx[i], xin(i));
     t = wave_sum(t) * rs;
   }
-  head_publish(c, s, t, n_valid, logits, cb);
+  head_publish<C0>(c, s, t, n_valid, logits, cb);
   (void)W;
 }
 // A head's rows of this WG -- s: row 8w + wave, t: row 2048 + w (wave 0 of WGs 0-2) -- -> logits taps
 // and the hand-off: arg-max keys (E6), Gumbel-max keys, or every logit (sampling with a top-k)
+template <bool C0>
 __device__ __forceinline__ void head_publish(Ctx& c, float s, float t, int n_valid, float* logits, int cb) {
   const int row = 8 * c.w + c.wave;
+  if constexpr (C0) {
+    // mlx_lm logits processors on c0 (c0_process.h), before the tap and every publication; a branch on
+    // kernel arguments, so a frame without processors runs what it always ran
+    if (c.p.c0_bias || c.p.c0_penalty > 0.f) {
+      const int n = c0_window_n(c.p.frame_ctr[0], c.p.c0_context, c.p.c0_penalty);
+      s = c0_processed(s, row, c.p.c0_bias, c.L.c0b[c.wave], c.L.c0win, n, c.p.c0_penalty);
+      if (c.wave == 0 && c.w < 3) t = c0_processed(t, 2048 + c.w, c.p.c0_bias, c.L.c0b[8], c.L.c0win, n, c.p.c0_penalty);
+    }
+  }
   unsigned long long best = row < n_valid ? pack_argmax(s, row) : 0ull;
   if (c.lane == 0 && row < n_valid) logits[row] = s;
   const int xr = 2048 + c.w;
@@ -1242,6 +1258,21 @@ __device__ __forceinline__ void run_step(Ctx& c, int step, PreT<Q4>& r) {
   if (step + 1 < p.K) kv_store(c, step + 1, kv0);  // and in LDS before the loop back-edge
 }
 
+// Logits processors on c0: the bias of this WG's codebook0_head rows and the utterance's repetition window
+// (the c0 column of the code history's last frames) -> LDS.  Issued with the frame start's weight loads and
+// complete at the barrier the staging of h_last needs anyway, so head_publish waits for neither.
+__device__ __forceinline__ void c0_stage(Ctx& c) {
+  const DecFrameArgs& p = c.p;
+  if (p.c0_bias && c.tid < 9) {
+    const int v = c.tid < 8 ? 8 * c.w + c.tid : 2048 + c.w;
+    c.L.c0b[c.tid] = v < p.VP ? p.c0_bias[v] : 0.f;
+  }
+  if (p.c0_penalty > 0.f) {
+    const int f = p.frame_ctr[0];
+    if (c.tid < c0_window_n(f, p.c0_context, p.c0_penalty)) c.L.c0win[c.tid] = c0_window_code(p.hist, f, c.tid, 0, 1, p.K);
+  }
+}
+
 // Frame start of the int4 kernel: codebook0_head (one 2048-wide row per wave: a chunk per lane) and the
 // projection of h_last (waves 0-3, rows 4w + v) against h_last staged in the padded layout -> the same
 // two hand-offs as the bf16 kernel's frame start
@@ -1275,11 +1306,12 @@ __device__ __forceinline__ void frame_start4(Ctx& c) {
     sum += __shfl_xor(sum, 8, 64);
     if ((c.tid & 15) == 0) L.h0.hh[k >> 5] = sum;
   }
+  c0_stage(c);
   __syncthreads();
   const float s = wave_sum(q4dot32(ha, L.h0.hq[c.lane], hs, L.h0.hh[c.lane]));
   float t = 0.f;
   if (c.wave == 0 && c.w < 3) t = wave_sum(q4dot32(hx, L.h0.hq[c.lane], hxs, L.h0.hh[c.lane]));
-  head_publish(c, s, t, p.V, p.c0_logits, 0);  // -> G_ARG (hand-off 0)
+  head_publish<true>(c, s, t, p.V, p.c0_logits, 0);  // -> G_ARG (hand-off 0)
   const float pv = wave_sum(q4dot32(pa, L.h0.hq[c.lane], ps, L.h0.hh[c.lane]));
   if (c.lane == 0 && c.wave < 4) L.wsum[c.wave][0] = pv;
   __syncthreads();
@@ -1322,8 +1354,9 @@ __global__ __launch_bounds__(NT, 1) void dec_frame_kernel(DecFrameArgs p) {
   load_qkv(c, 0, r.wq);
   load_o(c, 0, r.wo);
   for (int k = c.tid; k < DB; k += NT) L.xn[0][k] = p.h_last[k];
+  c0_stage(c);
   __syncthreads();
-  phase_head<DB>(c, p.c0_head, p.V, c0a, c0x, p.c0_logits, 0);  // -> G_ARG (hand-off 0)
+  phase_head<DB, false, true>(c, p.c0_head, p.V, c0a, c0x, p.c0_logits, 0);  // -> G_ARG (hand-off 0)
   {
     float s = dot8(pa[0], L.xn[0] + 8 * (128 * (c.wave & 1) + c.lane)) + dot8(pa[1], L.xn[0] + 8 * (128 * (c.wave & 1) + c.lane + 64));
     s = wave_sum(s);

@@ -92,6 +92,14 @@ int csm_begin(csm_engine* e, int B, const uint64_t* seeds, float temperature, in
  * before the Gumbel-max draw (oracle/csm_oracle.py filter_keep).  top_p in (0, 1) and min_p != 0 are
  * active; call after csm_begin, before the first frame (csm_begin resets them to off). */
 int csm_set_sampler_filters(csm_engine* e, double top_p, double min_p, int min_tokens_to_keep);
+/* mlx_lm make_logits_processors on the c0 logits (generation.py:44-49), run inside the frame: first
+ * logits[bias_idx[i]] += bias_val[i] (n_bias 0: no bias), then for every code t among the utterance's last
+ * repetition_context_size c0 codes of this generation, once per distinct t, logits[t] * penalty when
+ * negative, else logits[t] / penalty (penalty 0: none); all float32.  CSM_ERR_ARG for an index outside
+ * [0, n_audio_vocab), a penalty < 0 or a context < 0 or above the device cap of 256.
+ * Call after csm_begin, before the first frame (csm_begin resets to off). */
+int csm_set_c0_processors(csm_engine* e, int n_bias, const int32_t* bias_idx, const float* bias_val,
+                          float repetition_penalty, int repetition_context_size);
 /* Prompt rows of utterance b: tokens/mask [T][K+1] (text id in the last column). */
 int csm_prefill(csm_engine* e, int b, int T, const int32_t* tokens, const uint8_t* mask);
 /* csm_prefill for several utterances at once (the rows of generate_batch's prompts): utts[i] gets
@@ -120,7 +128,9 @@ int csm_frame_step(csm_engine* e, int32_t* out_codes, uint8_t* done);
  * csm_frame_c0_logits runs the backbone step + codebook0_head and copies logits [B][V] out;
  * csm_frame_finish takes the (processed) logits [B][V] back, picks c0 (arg-max when greedy, else the
  * engine's sampler) and runs the 31 decoder steps.  Replaces generate_frame's processor loop
- * (generation.py:44-49) -- called once per frame instead of csm_run_frames. */
+ * (generation.py:44-49) -- called once per frame instead of csm_run_frames.  mlx_lm's two standard
+ * processors (logit_bias, repetition_penalty) no longer need it: csm_set_c0_processors runs them inside
+ * the frame; this pair remains for arbitrary host callables. */
 int csm_frame_c0_logits(csm_engine* e, float* logits);
 int csm_frame_finish(csm_engine* e, const float* logits, int* all_done);
 /* A frame sampled on the host by an arbitrary sampler callable (the sampler= keyword the reference CLI
