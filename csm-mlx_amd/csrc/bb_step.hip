@@ -36,14 +36,12 @@ constexpr int NWG = BB_STEP_WGS, NT = BB_STEP_THREADS;
 constexpr int D = 2048, F = 8192, HQ = 32, HKV = 8, HD = 64, NL = BB_STEP_LAYERS;
 constexpr int QKV = (HQ + 2 * HKV) * HD;  // 3072
 constexpr int NATT = HQ;                  // attention workgroups: one per query head
-constexpr unsigned SPIN_LIMIT = 1u << 22; // ~0.1 s of s_sleep per hand-off before declaring failure
 
 // granule regions (u64 offsets), double-buffered by hand-off parity.  The all-gather regions (E2,
 // E3, E5: every workgroup reads every granule) are written in REP replicas, workgroup w reading
-// replica w % REP (dec_frame.hip: fewer readers per granule; speed only, never correctness).
+// replica w % REP (handoff.h HandoffCtx: fewer readers per granule; speed only, never correctness).
 // Measured: 581-584 us (REP 1 / 8) -> 569 us (REP 4) per row (profiles/r03_ab_replicas.txt).
 constexpr int REP = 4;
-__host__ __device__ constexpr size_t rs_of(size_t per) { return (per + 511) / 512 * 512 + 32; }
 constexpr size_t G_QKV = 0;                                   // [2][QKV]
 constexpr size_t G_ATT = G_QKV + 2 * QKV;                     // [2][REP][rs(D)]
 constexpr size_t G_X = G_ATT + 2 * REP * rs_of(D);            // [2][REP][rs(D)]
@@ -70,27 +68,7 @@ struct Lds {
   float ah[D / 32];
 };
 
-struct Ctx {
-  const BbStepArgs& p;
-  Lds& L;
-  int w, tid, lane, wave;
-  unsigned tag0;
-  int e;  // hand-off counter
-  __device__ void refresh() {
-    tid = opaque_tid();
-    lane = tid & 63;
-    wave = tid >> 6;
-  }
-  __device__ unsigned tag() const { return tag0 + (unsigned)e; }
-  __device__ u64* buf(size_t region, size_t per) const { return p.gbuf + region + (size_t)(e & 1) * per; }
-  // replicated all-gather regions: this workgroup's replica (reads), and a store to every replica
-  __device__ u64* rbuf(size_t region, size_t per) const {
-    return p.gbuf + region + ((size_t)(e & 1) * REP + (size_t)(w % REP)) * rs_of(per);
-  }
-  // one replica r of granule i (publishing lanes spread over the replicas: one store each)
-  __device__ void put(size_t region, size_t per, size_t i, float v, int r) const {
-    gput(p.gbuf + region + ((size_t)(e & 1) * REP + (size_t)r) * rs_of(per) + i, v, tag());
-  }
+struct Ctx : HandoffCtx<BbStepArgs, Lds, REP> {
   // profiling: the 100 MHz real-time clock when this WG passed hand-off e (slot e + 1; slot 0 = start)
   __device__ void stamp(int slot) const {
     if (p.stamps && tid == 0 && slot < BB_STEP_STAMPS) p.stamps[(size_t)w * BB_STEP_STAMPS + slot] = __builtin_amdgcn_s_memrealtime();
@@ -104,7 +82,6 @@ constexpr int PROBE_DELAY = 32;
 // the E2 wait of the 224 workgroups that run no attention (they wait the whole attention): no longer
 // delay measured better
 constexpr int DELAY_E2 = PROBE_DELAY;
-__device__ __forceinline__ bool spin_fail(Ctx& c, unsigned spin) { return handoff::spin_fail(c.p.err, SPIN_LIMIT, spin); }
 
 // Wait until granules [0, n) of buf carry this hand-off's tag; values -> out (LDS).  One 8-B load per
 // granule (thread t: granules t + NT u): the bf16 kernel's E2 wait.  Not handoff.h poll_granules: an
@@ -508,15 +485,11 @@ __device__ __forceinline__ void load_m4(Ctx& c, int l, WM4& r) {
   }
 }
 
-// half-group sums of the staged pair (2t, 2t + 1) of each half: the 16 threads of a half group in order
+// half-group sums of the staged pair (2t, 2t + 1) of each half
 __device__ __forceinline__ void half_group_sums(Ctx& c, const float (&pair)[2], float* out) {
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    float v = pair[h];
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
+    const float v = sum16(pair[h]);
     if ((c.tid & 15) == 0) out[(h * (D / 2) + 2 * c.tid) >> 5] = v;
   }
 }
@@ -648,7 +621,7 @@ __device__ __forceinline__ void phase_m4(Ctx& c, const WM4& W, float (&acc)[4], 
 
 __global__ __launch_bounds__(NT, 1) void bb_step_q4_kernel(BbStepArgs p) {
   __shared__ __attribute__((aligned(16))) Lds L;
-  Ctx c{p, L, (int)blockIdx.x, (int)threadIdx.x, (int)(threadIdx.x & 63), (int)(threadIdx.x >> 6), 0u, 0};
+  Ctx c{{p, L, (int)blockIdx.x, (int)threadIdx.x, (int)(threadIdx.x & 63), (int)(threadIdx.x >> 6), 0u, 0}};
   c.tag0 = __hip_atomic_load(p.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
   c.stamp(0);
   const int pos = p.pos[0];
@@ -715,7 +688,7 @@ namespace {
 
 __global__ __launch_bounds__(NT, 1) void bb_step_kernel(BbStepArgs p) {
   __shared__ __attribute__((aligned(16))) Lds L;
-  Ctx c{p, L, (int)blockIdx.x, (int)threadIdx.x, (int)(threadIdx.x & 63), (int)(threadIdx.x >> 6), 0u, 0};
+  Ctx c{{p, L, (int)blockIdx.x, (int)threadIdx.x, (int)(threadIdx.x & 63), (int)(threadIdx.x >> 6), 0u, 0}};
   c.tag0 = __hip_atomic_load(p.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
   c.stamp(0);
   const int pos = p.pos[0];  // the new row's position (the embedding launch advanced it)

@@ -91,7 +91,7 @@ __device__ __forceinline__ float key2f(uint32_t k) {
 }
 // The sampler's counter-based Gumbel-max (restated in oracle/csm_oracle.py gumbel_u): one key per
 // (utterance seed, frame * K + codebook), one uniform per vocabulary entry, perturbed logit in double.
-// Shared by sample_kernel and the persistent frame decoder so both pick identical codes.
+// Shared by every sampler (sampler.h and its callers) so all pick identical codes.
 __device__ __forceinline__ uint64_t gumbel_key(uint64_t seed, int step) {
   return splitmix64(splitmix64(seed) ^ (uint64_t)step);
 }
@@ -500,7 +500,7 @@ struct DecStepXsArgs {
   float* head_out;
   unsigned long long* head_part;
   // sampled steps (temperature > 0, top-k only; needs the head in the launch): workgroup m < M samples
-  // row m from the head's logits as sample_kernel does (radix-select top-k threshold, Gumbel-max with
+  // row m from the head's logits by the sampler of sampler.h (radix-select top-k threshold, Gumbel-max with
   // the counter key(seeds[m], frame_ctr[0] * K + cb)) -> codes[m][cb] and the single partial head_part[m][0]
   int sample, s_top_k, s_K, s_cb;
   float s_temperature;

@@ -15,6 +15,7 @@
 #include "c0_process.h"
 #include "csm_kernels.h"
 #include "engine_util.h"
+#include "sampler.h"
 #include "xs.h"
 
 #include <cstdlib>
@@ -998,80 +999,13 @@ __global__ __launch_bounds__(256) void rmsnorm_rows_kernel(const float* x, int x
 
 // ============================================================================ sampling
 
-// (value, index) arg-max with the first-max tie rule of mx.argmax
-template <typename T>
-__device__ __forceinline__ void argmax_merge(T& v, int& i, T ov, int oi) {
-  if (ov > v || (ov == v && oi < i)) {
-    v = ov;
-    i = oi;
-  }
-}
-template <typename T>
-__device__ __forceinline__ int block_argmax(T v, int i, T* sv, int* si) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const T ov = __shfl_xor(v, o, 64);
-    const int oi = __shfl_xor(i, o, 64);
-    argmax_merge(v, i, ov, oi);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    sv[wave] = v;
-    si[wave] = i;
-  }
-  __syncthreads();
-  T bv = sv[0];
-  int bi = si[0];
-  for (int w = 1; w < 4; ++w) argmax_merge(bv, bi, sv[w], si[w]);
-  return bi;
-}
-
 // One block per utterance.  Greedy: first max (mx.argmax, generation.py:51-52).  Else Gumbel-max
 // over logits*(1/temp) restricted to values >= the top_k-th largest (radix select) -- mlx_lm
 // make_sampler(temp, top_k) semantics with the build's counter-based RNG.  The chosen code's
 // audio embedding (embed_audio, models.py:79-80) is gathered into the next decoder input row.
-constexpr int SAMPLE_NPT = 16;  // logits per thread: V <= 4096 (checked at launch)
+// The threshold, the arg-max and the Gumbel pass are sampler.h's.
+using namespace sampler;
 constexpr int SAMPLE_CMAX = 512;  // compacted top-k survivors (more ties than this: the in-place loop)
-// The top_k-th largest of a 256-thread block's logits (lv[i] = logit tid + 256 i, i < SAMPLE_NPT):
-// radix select of its order-preserving key, 8 bits per pass; the digit is found by a parallel suffix
-// count over the 256 bins (thread t holds digit 255 - t), not a serial scan.  Every logit >= the
-// result is in the top-k set (ties at the k-th value kept).
-__device__ float topk_threshold_256(const float (&lv)[SAMPLE_NPT], int V, int k, uint32_t* hist, uint32_t* wsum,
-                                    uint32_t* sh) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  uint32_t prefix = 0, maskbits = 0, rem = (uint32_t)k;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    hist[tid] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < SAMPLE_NPT; ++i) {
-      const uint32_t key = f2key(lv[i]);
-      if (tid + 256 * i < V && (key & maskbits) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    const uint32_t h = hist[255 - tid];
-    uint32_t c = h;  // inclusive prefix over t = count of keys with digit >= 255 - t
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t u = __shfl_up(c, o, 64);
-      if (lane >= o) c += u;
-    }
-    if (lane == 63) wsum[wave] = c;
-    __syncthreads();
-    for (int w = 0; w < wave; ++w) c += wsum[w];
-    const uint32_t above = c - h;
-    if (h > 0 && above < rem && rem <= c) {  // exactly one digit
-      sh[0] = prefix | ((uint32_t)(255 - tid) << shift);
-      sh[1] = rem - above;
-    }
-    __syncthreads();
-    prefix = sh[0];
-    rem = sh[1];
-    maskbits |= 255u << shift;
-    __syncthreads();  // hist / sh reused by the next pass
-  }
-  return key2f(prefix);
-}
 
 template <typename WT>
 __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
@@ -1104,7 +1038,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
         bi = v;
       }
     }
-    code = block_argmax<float>(best, bi, sfv, si);
+    code = block_argmax<float, 4>(tid, best, bi, sfv, si);
   } else {
     // the row's logits stay in registers for the radix passes and the Gumbel pass
     float lv[SAMPLE_NPT];
@@ -1114,7 +1048,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
       lv[i] = v < V ? lg[v] : 0.f;
     }
     const bool topk = p.top_k > 0 && p.top_k < V;
-    const float thr = topk ? topk_threshold_256(lv, V, p.top_k, hist, wsum, sh) : -INFINITY;
+    const float thr = topk ? topk_threshold<256, SAMPLE_NPT>(tid, V, p.top_k, hist, wsum, sh, RegSlots<SAMPLE_NPT>{lv}) : -INFINITY;
     const uint64_t key = gumbel_key(p.seeds[b], p.frame_ctr[0] * p.K + p.cb);
     const float inv_t = 1.0f / p.temperature;
     double best = -INFINITY;
@@ -1169,22 +1103,12 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
         }
       }
     } else {
-#pragma unroll
-      for (int i = 0; i < SAMPLE_NPT; ++i) {
-        const int v = tid + 256 * i;
-        const float l = lv[i];
-        if (v >= V || !(l >= thr)) continue;
-        const double val = gumbel_perturbed(l, inv_t, key, v);
-        if (val > best) {
-          best = val;
-          bi = v;
-        }
-      }
+      gumbel_pass<256, SAMPLE_NPT>(tid, V, thr, inv_t, RegSlots<SAMPLE_NPT>{lv},
+                                   [&](int, int v) { return gumbel_noise(key, v); }, best, bi);
     }
-    code = block_argmax<double>(best, bi, sdv, si);
+    code = block_argmax<double, 4>(tid, best, bi, sdv, si);
   }
-  // NaN logits leave no winner; clamp so a bad row can never index outside the embedding table
-  code = min(max(code, 0), V - 1);
+  code = clamp_code(code, V);
   if (tid == 0) {
     p.codes[(size_t)b * p.K + p.cb] = code;
     if (p.part) p.part[(size_t)b * p.part_stride] = pack_argmax(0.f, code);  // consumed as a 1-entry partial
@@ -1220,7 +1144,8 @@ __global__ __launch_bounds__(256) void sample_filtered_kernel(SampleParams p) {
     lgs[v] = lv[i];
     keep[v] = 0;
   }
-  const float thr = (p.top_k > 0 && p.top_k < V) ? topk_threshold_256(lv, V, p.top_k, hist, wsum, sh) : -INFINITY;
+  const float thr =
+      (p.top_k > 0 && p.top_k < V) ? topk_threshold<256, SAMPLE_NPT>(tid, V, p.top_k, hist, wsum, sh, RegSlots<SAMPLE_NPT>{lv}) : -INFINITY;
   // lse = max + log(sum exp(l - max)) over the valid logits (per-thread sums in i order, waves by
   // DPP reductions, the 4 waves in order)
   float mx = -INFINITY;
@@ -1332,12 +1257,12 @@ __global__ __launch_bounds__(256) void sample_filtered_kernel(SampleParams p) {
       bi = v;
     }
   }
-  int code = block_argmax<double>(best, bi, sdv, si);
+  int code = block_argmax<double, 4>(tid, best, bi, sdv, si);
   if (code == 0x7fffffff) {
     __syncthreads();
-    code = block_argmax<float>(bl, bli, fred, si);
+    code = block_argmax<float, 4>(tid, bl, bli, fred, si);
   }
-  code = min(max(code, 0), V - 1);
+  code = clamp_code(code, V);
   if (tid == 0) {
     p.codes[(size_t)b * p.K + p.cb] = code;
     if (p.part) p.part[(size_t)b * p.part_stride] = pack_argmax(0.f, code);

@@ -37,6 +37,7 @@
 #include "c0_process.h"
 #include "csm_kernels.h"
 #include "handoff.h"
+#include "sampler.h"
 
 namespace {
 
@@ -46,7 +47,6 @@ constexpr int NWG = 256, NT = 512;
 constexpr int D = 1024, F = 8192, HQ = 8, HKV = 2, HD = 128, NL = DEC_FRAME_LAYERS, DB = 2048;
 constexpr int QKV = (HQ + 2 * HKV) * HD;  // 1536
 constexpr int MAXM = 2;                   // rows per step (step 1: [h_last, E_a[c0]])
-constexpr unsigned SPIN_LIMIT = 1u << 22; // ~0.1 s of s_sleep per hand-off before declaring failure
 constexpr int VMAX = 2056;                // padded audio vocabulary (V <= 2051, checked by the engine)
 
 // the same chunk against two activation rows (every weight converted once, used twice: no
@@ -105,7 +105,6 @@ struct Lds {
   };
   float Vs[HKV][32][HD];    // cached values
   float lg[VMAX];          // sampling: the head's logits, gathered from every workgroup
-  int code;                // last arg-max
   int flag;
   // int4 kernel: projection inputs in the padded layout with their half-group sums -- x * norm weight
   // (QKV / gate-up / head input) and the attention output (o_proj input)
@@ -127,13 +126,12 @@ namespace {
 // granule REP times, workgroup w polls replica w % REP -- the workgroups of one XCD under the
 // observed round-robin placement (speed only, never correctness), so each granule has 256 / REP
 // readers instead of 256 (MI355X_MICROARCH.md allgather row: 256 -> 32 readers of a 16 KB sweep
-// -1.9 us).  Replicas are 4 KB-aligned plus a 256-B skew so they fall on different channels.
+// -1.9 us).  The addressing is handoff.h HandoffCtx (rs_of: the replica stride).
 // The reduce-scatter region (G_PART: each granule has one reader) is not replicated.  Measured
 // (profiles/r03_ab_replicas.txt): 2394 -> 2325 us per frame at REP 4 or 8 with the replica stores
 // spread over lanes (stored serially by one lane, REP 8 cost more on the publish than it saved).
 constexpr int REP = 4;
-__host__ __device__ constexpr size_t rs_of(size_t per) { return (per + 511) / 512 * 512 + 32; }
-constexpr size_t G_X = 0;                                               // [2][REP][rs(MAXM*D)] x slices
+constexpr size_t G_X = 0;                                              // [2][REP][rs(MAXM*D)] x slices
 constexpr size_t G_QKV = G_X + 2 * REP * rs_of(MAXM * D);               // [2][REP][rs(MAXM*QKV)]
 constexpr size_t G_PART = G_QKV + 2 * REP * rs_of(MAXM * QKV);          // [2][NWG][MAXM][D] down partials
 constexpr size_t G_ARG = G_PART + (size_t)2 * NWG * MAXM * D;           // [2][REP][rs(NWG*2)] arg-max keys
@@ -141,12 +139,7 @@ constexpr size_t G_LOG = G_ARG + 2 * REP * rs_of(NWG * 2);              // [2][R
 constexpr size_t G_GUM = G_LOG + 2 * REP * rs_of(VMAX);               // [2][REP][rs(NWG*3)] Gumbel-max keys
 constexpr size_t G_TOTAL = G_GUM + 2 * REP * rs_of(NWG * 3);
 
-struct Ctx {
-  const DecFrameArgs& p;
-  Lds& L;
-  int w, tid, lane, wave;
-  unsigned tag0;
-  int e;  // hand-off counter
+struct Ctx : HandoffCtx<DecFrameArgs, Lds, REP> {
   int ps = 0;  // phase-mark counter (profiling stamps 512..1007)
   int code = 0;  // the last head's code (every thread holds it)
   __device__ void mark() {
@@ -156,25 +149,6 @@ struct Ctx {
   // profiling: the 100 MHz real-time clock when this WG's hand-off wait number e completed
   __device__ void stamp() const {
     if (p.stamps && tid == 0 && e < DEC_FRAME_STAMPS) p.stamps[(size_t)w * DEC_FRAME_STAMPS + e] = __builtin_amdgcn_s_memrealtime();
-  }
-  __device__ void refresh() {
-    tid = opaque_tid();
-    lane = tid & 63;
-    wave = tid >> 6;
-  }
-  __device__ unsigned tag() const { return tag0 + (unsigned)e; }
-  __device__ u64* buf(size_t region, size_t per) const { return p.gbuf + region + (size_t)(e & 1) * per; }
-  // replicated all-gather regions: this workgroup's replica (reads), and a store to every replica
-  __device__ u64* rbuf(size_t region, size_t per) const {
-    return p.gbuf + region + ((size_t)(e & 1) * REP + (size_t)(w % REP)) * rs_of(per);
-  }
-  // one replica r of granule i: the publishing lanes are spread over the replicas (lane-parallel
-  // stores, one per lane), so a hand-off costs its producer one store instruction, not REP
-  __device__ void put(size_t region, size_t per, size_t i, float v, int r) const {
-    gput(p.gbuf + region + ((size_t)(e & 1) * REP + (size_t)r) * rs_of(per) + i, v, tag());
-  }
-  __device__ void put_u(size_t region, size_t per, size_t i, unsigned v, int r) const {
-    gput_u(p.gbuf + region + ((size_t)(e & 1) * REP + (size_t)r) * rs_of(per) + i, v, tag());
   }
 };
 
@@ -190,7 +164,6 @@ constexpr int DELAY_E1 = PROBE_DELAY, DELAY_E3 = PROBE_DELAY, DELAY_E4 = PROBE_D
 // probes, not faster ones (profiles/r03_ab_poll.txt)
 constexpr int REPOLL = 2;
 
-__device__ __forceinline__ bool spin_fail(Ctx& c, unsigned spin) { return handoff::spin_fail(c.p.err, SPIN_LIMIT, spin); }
 // use(x): the lane-local consumption of the matched probe
 template <int GPT, int DELAY = PROBE_DELAY, typename F>
 __device__ __forceinline__ void poll(Ctx& c, const u64* base, const int (&off)[GPT], const bool (&val)[GPT], F&& use) {
@@ -392,12 +365,9 @@ __device__ __forceinline__ void load_dn4(Ctx& c, int l, WDn4& r) {
   }
 }
 
-// half-group sums of the pair (2t, 2t + 1) of one 1024-wide row: the 16 threads of a half group in order
+// half-group sums of the pair (2t, 2t + 1) of one 1024-wide row
 __device__ __forceinline__ void half_group_sum16(const Ctx& c, float v, float* out) {
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  v += __shfl_xor(v, 8, 64);
+  v = sum16(v);
   if ((c.tid & 15) == 0) out[c.tid >> 4] = v;
 }
 
@@ -954,12 +924,13 @@ __device__ __forceinline__ int gather_code(Ctx& c, int V) {
   return c.code;
 }
 
-// Sampling (temperature > 0): gather the head's V logits, then -- identically in every workgroup --
-// the sampler of sample_kernel (csm_kernels.hip): the top_k-th largest logit by radix select (keys
-// >= it kept, ties included), then the Gumbel-max over logits * (1/temp) of the kept entries with
-// the first-max tie rule.  cb: codebook index of the sampler's counter (frame * K + cb).
+// Sampling (temperature > 0) with top-k: gather the head's V logits, then -- identically in every
+// workgroup -- the sampler of sampler.h over L.lg.  cb: codebook index of the sampler's counter
+// (frame * K + cb).
 __device__ __forceinline__ int sample_code(Ctx& c, int V, int cb) {
-  constexpr int NPT = (VMAX + NT - 1) / NT;  // logits per thread
+  constexpr int NPT = sampler::DEC_FRAME_SAMPLE_NPT;
+  static_assert(VMAX <= NT * NPT, "a slot for every logit");
+  static_assert(sizeof(sampler::Scratch<NT / 64>) <= sizeof(Lds::red), "the sampler borrows L.red");
   const DecFrameArgs& p = c.p;
   // the Gumbel noise does not depend on the logits: drawn before the hand-off wait (overlaps it)
   const uint64_t key = gumbel_key(p.seeds[0], p.frame_ctr[0] * p.K + cb);
@@ -970,92 +941,20 @@ __device__ __forceinline__ int sample_code(Ctx& c, int V, int cb) {
     gn[i] = v < V ? gumbel_noise(key, v) : 0.0;
   }
   gather<NPT>(c, c.rbuf(G_LOG, VMAX), V, c.L.lg);
+  sampler::Scratch<NT / 64>& S = *reinterpret_cast<sampler::Scratch<NT / 64>*>(&c.L.red[0][0]);
+  auto logit = [&](int i) { return c.L.lg[c.tid + NT * i]; };
   float thr = -INFINITY;
-  if (p.top_k > 0 && p.top_k < V) {
-    // radix select, 8 bits per pass; threads 0..255 hold digit 255 - tid for the suffix count
-    uint32_t* hist = reinterpret_cast<uint32_t*>(&c.L.red[0][0]);
-    uint32_t* wsum = hist + 256;
-    uint32_t* sh = hist + 264;  // [prefix, remain]
-    uint32_t prefix = 0, maskbits = 0, rem = (uint32_t)p.top_k;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      if (c.tid < 256) hist[c.tid] = 0;
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < NPT; ++i) {
-        const int v = c.tid + NT * i;
-        if (v < V) {
-          const uint32_t key = f2key(c.L.lg[v]);
-          if ((key & maskbits) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-        }
-      }
-      __syncthreads();
-      uint32_t h = 0, cnt = 0;
-      if (c.tid < 256) {
-        h = hist[255 - c.tid];
-        cnt = h;  // inclusive prefix over t = count of keys with digit >= 255 - t
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const uint32_t u = __shfl_up(cnt, o, 64);
-          if (c.lane >= o) cnt += u;
-        }
-        if (c.lane == 63) wsum[c.wave] = cnt;
-      }
-      __syncthreads();
-      if (c.tid < 256) {
-        for (int w = 0; w < c.wave; ++w) cnt += wsum[w];
-        const uint32_t above = cnt - h;
-        if (h > 0 && above < rem && rem <= cnt) {  // exactly one digit
-          sh[0] = prefix | ((uint32_t)(255 - c.tid) << shift);
-          sh[1] = rem - above;
-        }
-      }
-      __syncthreads();
-      prefix = sh[0];
-      rem = sh[1];
-      maskbits |= 255u << shift;
-      __syncthreads();  // sh / hist reused by the next pass
-    }
-    thr = key2f(prefix);
-  }
-  const float inv_t = 1.0f / p.temperature;
-  double best = -INFINITY;
-  int bi = 0x7fffffff;
-#pragma unroll
-  for (int i = 0; i < NPT; ++i) {
-    const int v = c.tid + NT * i;
-    if (v >= V) continue;
-    const float l = c.L.lg[v];
-    if (!(l >= thr)) continue;
-    const double val = (double)(l * inv_t) + gn[i];  // = gumbel_perturbed(l, inv_t, key, v)
-    if (val > best) {  // increasing v per thread: first max kept
-      best = val;
-      bi = v;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  double* sv = reinterpret_cast<double*>(&c.L.wsum[0][0]);
-  int* si = reinterpret_cast<int*>(sv + 8);
-  if (c.lane == 0) { sv[c.wave] = best; si[c.wave] = bi; }
-  __syncthreads();
-  if (c.tid == 0) {
-    double bv = sv[0];
-    int b = si[0];
-    for (int w2 = 1; w2 < NT / 64; ++w2)
-      if (sv[w2] > bv || (sv[w2] == bv && si[w2] < b)) { bv = sv[w2]; b = si[w2]; }
-    c.L.code = min(max(b, 0), V - 1);  // NaN logits leave no winner: clamp (as sample_kernel)
-  }
-  __syncthreads();
-  c.code = c.L.code;
+  if (p.top_k > 0 && p.top_k < V) thr = sampler::topk_threshold<NT, NPT>(c.tid, V, p.top_k, S.hist, S.wsum, S.sh, logit);
+  double best;
+  int bi;
+  sampler::gumbel_pass<NT, NPT>(c.tid, V, thr, 1.0f / p.temperature, logit, [&](int i, int) { return gn[i]; }, best, bi);
+  c.code = sampler::clamp_code(sampler::block_argmax<double, NT / 64>(c.tid, best, bi, S.bv, S.bi), V);
+  __syncthreads();  // L.red is free again
   return c.code;
 }
 
 // Gather the 256 workgroups' Gumbel-max keys (value key hi, lo, index) -> code: max value, lowest
-// index on ties; no candidate anywhere (every logit NaN or -inf) -> V - 1, as sample_kernel.
+// index on ties; no candidate anywhere (every logit NaN or -inf) -> V - 1 (sampler.h clamp_code).
 __device__ __forceinline__ int gumbel_code(Ctx& c, int V) {
   constexpr int NG = NWG * 3, GPT = (NG + NT - 1) / NT;
   int off[GPT];
@@ -1325,7 +1224,7 @@ __device__ __forceinline__ void frame_start4(Ctx& c) {
 template <bool Q4>
 __global__ __launch_bounds__(NT, 1) void dec_frame_kernel(DecFrameArgs p) {
   __shared__ __attribute__((aligned(16))) Lds L;
-  Ctx c{p, L, (int)blockIdx.x, (int)threadIdx.x, (int)(threadIdx.x & 63), (int)(threadIdx.x >> 6), 0u, 0};
+  Ctx c{{p, L, (int)blockIdx.x, (int)threadIdx.x, (int)(threadIdx.x & 63), (int)(threadIdx.x >> 6), 0u, 0}};
   c.tag0 = __hip_atomic_load(p.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
   if (p.stamps && c.tid == 0) p.stamps[(size_t)c.w * DEC_FRAME_STAMPS + DEC_FRAME_STAMPS - 2] = __builtin_amdgcn_s_memrealtime();
   PreT<Q4> r;

@@ -46,6 +46,7 @@
 // rsqrt(sum x^2 / D + eps) after the dot product); softmax with max subtraction in fp32.
 #include "csm_kernels.h"
 #include "handoff.h"
+#include "sampler.h"
 #include "xs.h"
 
 namespace {
@@ -64,7 +65,6 @@ constexpr int NGRP = 8;                       // down K groups (1024 h columns e
 constexpr int O_WG0 = NQT;                    // o_proj workgroups 48 .. 79
 constexpr int A_WG0 = O_WG0 + 32;             // attention workgroups 80 .. 80 + MR - 1
 constexpr int RMAX = 64;                      // rows of the scratch buffers (row stride of sums)
-constexpr unsigned SPIN_LIMIT = 1u << 22;
 constexpr int SC1 = 16;  // buffer cache policy: sc1 (agent-coherent)
 static_assert(NWG == 256 && NWV == 8, "roles assume 256 workgroups of 8 waves");
 static_assert(KS_D == 2 * NWV && KS_F / NGRP == 2 * NWV, "every wave takes two K stages of its tile");
@@ -118,7 +118,6 @@ struct Ctx {
   }
 };
 
-__device__ __forceinline__ bool spin_fail(const Ctx& c, unsigned spin) { return handoff::spin_fail(c.p.err, SPIN_LIMIT, spin); }
 __device__ __forceinline__ unsigned ld_cw(const unsigned* a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // lanes < n of wave 0 wait until word idx(lane) has reached `target` (flags hold tags, tickets counts:
 // both only grow), then the workgroup barrier
@@ -756,13 +755,11 @@ __device__ __forceinline__ void role_h(Ctx& c, int t, const WTile<false> (&W)[2]
   }
 }
 
-// S (sampled steps; workgroup m < M, after its layers): row m's code from the head's logits -- the sampler
-// of sample_kernel (csm_kernels.hip) on 512 threads, as dec_frame.hip's sample_code: the top_k-th largest
-// logit by radix select (keys >= it kept, ties included), then the Gumbel-max of logit * (1 / T) + noise
-// over the kept entries, the lowest index on ties (the same winner whatever the visiting order) ->
-// codes[m][cb] and the 1-entry partial the next step reads.
+// S (sampled steps; workgroup m < M, after its layers): row m's code from the head's logits by the sampler
+// of sampler.h, the logits in registers -> codes[m][cb] and the 1-entry partial the next step reads.
 __device__ __forceinline__ void role_s(Ctx& c) {
   constexpr int NPT = DEC_XSD_SAMPLE_NPT;
+  static_assert(sizeof(sampler::Scratch<NWV>) <= sizeof(Lds::red), "the sampler borrows L.red");
   const DecStepXsArgs& p = c.p;
   const int m = c.w, V = p.n_valid;
   // the Gumbel noise does not depend on the logits: drawn before the wait
@@ -782,81 +779,15 @@ __device__ __forceinline__ void role_s(Ctx& c) {
     const int v = c.tid + NT * i;
     lg[i] = v < V ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, v * 4, 0, SC1)) : 0.f;
   }
+  sampler::Scratch<NWV>& S = *reinterpret_cast<sampler::Scratch<NWV>*>(&c.L.red[0][0][0][0]);
+  const sampler::RegSlots<NPT> logit{lg};
   float thr = -INFINITY;
-  uint32_t* hist = reinterpret_cast<uint32_t*>(&c.L.red[0][0][0][0]);
-  uint32_t* wsum = hist + 256;
-  uint32_t* sh = hist + 264;  // [prefix, remain]
-  if (p.s_top_k > 0 && p.s_top_k < V) {  // radix select, 8 bits per pass; threads 0..255 hold digit 255 - tid
-    uint32_t prefix = 0, maskbits = 0, rem = (uint32_t)p.s_top_k;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      if (c.tid < 256) hist[c.tid] = 0;
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < NPT; ++i) {
-        const int v = c.tid + NT * i;
-        if (v < V) {
-          const uint32_t k = f2key(lg[i]);
-          if ((k & maskbits) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
-        }
-      }
-      __syncthreads();
-      uint32_t h = 0, cnt = 0;
-      if (c.tid < 256) {
-        h = hist[255 - c.tid];
-        cnt = h;  // inclusive prefix over t = count of keys with digit >= 255 - t
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const uint32_t u = __shfl_up(cnt, o, 64);
-          if (c.lane >= o) cnt += u;
-        }
-        if (c.lane == 63) wsum[c.wave] = cnt;
-      }
-      __syncthreads();
-      if (c.tid < 256) {
-        for (int w = 0; w < c.wave; ++w) cnt += wsum[w];
-        const uint32_t above = cnt - h;
-        if (h > 0 && above < rem && rem <= cnt) {  // exactly one digit
-          sh[0] = prefix | ((uint32_t)(255 - c.tid) << shift);
-          sh[1] = rem - above;
-        }
-      }
-      __syncthreads();
-      prefix = sh[0];
-      rem = sh[1];
-      maskbits |= 255u << shift;
-      __syncthreads();  // hist / sh reused by the next pass
-    }
-    thr = key2f(prefix);
-  }
-  const float inv_t = 1.0f / p.s_temperature;
-  double best = -INFINITY;
-  int bi = 0x7fffffff;
-#pragma unroll
-  for (int i = 0; i < NPT; ++i) {
-    const int v = c.tid + NT * i;
-    if (v >= V || !(lg[i] >= thr)) continue;
-    const double val = (double)(lg[i] * inv_t) + gn[i];  // = gumbel_perturbed(l, inv_t, key, v)
-    if (val > best) {  // increasing v per thread: first max kept
-      best = val;
-      bi = v;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  double* sv = reinterpret_cast<double*>(hist + 272);
-  int* si = reinterpret_cast<int*>(sv + NWV);
-  if (c.lane == 0) { sv[c.wave] = best; si[c.wave] = bi; }
-  __syncthreads();
+  if (p.s_top_k > 0 && p.s_top_k < V) thr = sampler::topk_threshold<NT, NPT>(c.tid, V, p.s_top_k, S.hist, S.wsum, S.sh, logit);
+  double best;
+  int bi;
+  sampler::gumbel_pass<NT, NPT>(c.tid, V, thr, 1.0f / p.s_temperature, logit, [&](int i, int) { return gn[i]; }, best, bi);
+  const int code = sampler::clamp_code(sampler::block_argmax<double, NWV>(c.tid, best, bi, S.bv, S.bi), V);
   if (c.tid == 0) {
-    double bv = sv[0];
-    int b = si[0];
-    for (int w2 = 1; w2 < NWV; ++w2)
-      if (sv[w2] > bv || (sv[w2] == bv && si[w2] < b)) { bv = sv[w2]; b = si[w2]; }
-    const int code = min(max(b, 0), V - 1);  // NaN logits leave no winner: clamp (as sample_kernel)
     p.codes[(size_t)m * p.codes_K + p.s_cb] = code;
     p.head_part[(size_t)m * p.part_stride] = pack_argmax(0.f, code);  // consumed as a 1-entry partial
   }

@@ -65,6 +65,52 @@ __device__ __forceinline__ bool spin_fail(int* err, unsigned limit, unsigned spi
   }
   return false;
 }
+// ... bound to a kernel's context (its args carry the error word)
+constexpr unsigned SPIN_LIMIT = 1u << 22;  // ~0.1 s of s_sleep per hand-off before declaring failure
+template <typename C>
+__device__ __forceinline__ bool spin_fail(const C& c, unsigned spin) { return spin_fail(c.p.err, SPIN_LIMIT, spin); }
+
+// threadIdx.x through an opaque move: lane-dependent addresses derived from it inside the frame loop
+// are recomputed per iteration instead of being hoisted out of the loop and held (spilled) for the
+// whole frame.
+__device__ __forceinline__ int opaque_tid() {
+  int t;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"((int)threadIdx.x));
+  return t;
+}
+
+// The hand-off context of the persistent single-row kernels (dec_frame.hip, bb_step.hip): workgroup w's
+// view of the granule buffer p.gbuf at hand-off number e.  A region is double-buffered by hand-off parity.
+// An all-gather region (every workgroup reads every granule) is written in REP replicas, each
+// rs_of(per) granules apart -- 4 KB-aligned plus a 256-B skew, so the replicas fall on different
+// channels -- and workgroup w polls replica w % REP (speed only, never correctness).
+__host__ __device__ constexpr size_t rs_of(size_t per) { return (per + 511) / 512 * 512 + 32; }
+template <typename Args, typename Lds, int REP>
+struct HandoffCtx {
+  const Args& p;
+  Lds& L;
+  int w, tid, lane, wave;
+  unsigned tag0;
+  int e;  // hand-off counter
+  __device__ void refresh() {
+    tid = opaque_tid();
+    lane = tid & 63;
+    wave = tid >> 6;
+  }
+  __device__ unsigned tag() const { return tag0 + (unsigned)e; }
+  __device__ u64* buf(size_t region, size_t per) const { return p.gbuf + region + (size_t)(e & 1) * per; }
+  // replicated regions: replica r, this workgroup's replica (reads), and a store to one replica r of
+  // granule i -- the publishing lanes are spread over the replicas (lane-parallel stores, one per lane),
+  // so a hand-off costs its producer one store instruction, not REP
+  __device__ u64* rbuf(size_t region, size_t per, int r) const {
+    return p.gbuf + region + ((size_t)(e & 1) * REP + (size_t)r) * rs_of(per);
+  }
+  __device__ u64* rbuf(size_t region, size_t per) const { return rbuf(region, per, w % REP); }
+  __device__ void put(size_t region, size_t per, size_t i, float v, int r) const { gput(rbuf(region, per, r) + i, v, tag()); }
+  __device__ void put_u(size_t region, size_t per, size_t i, unsigned v, int r) const {
+    gput_u(rbuf(region, per, r) + i, v, tag());
+  }
+};
 
 // Wait until this thread's granules base[off[u]] (u < GPT, val[u]) carry `tag`, then use(probe).
 // One probe, its stale granules re-polled.  The first probe's loads are unconditional (an unused
@@ -182,14 +228,14 @@ __device__ __forceinline__ float2 half_sums(float v) {
   v += dpp_f<0xB1>(v);
   return make_float2(lane_f(v, 0) + lane_f(v, 16), lane_f(v, 32) + lane_f(v, 48));
 }
-
-// threadIdx.x through an opaque move: lane-dependent addresses derived from it inside the frame loop
-// are recomputed per iteration instead of being hoisted out of the loop and held (spilled) for the
-// whole frame.
-__device__ __forceinline__ int opaque_tid() {
-  int t;
-  asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"((int)threadIdx.x));
-  return t;
+// sum over each aligned group of 16 lanes, to all of them: a half group's 32 elements held as one pair
+// (2t, 2t + 1) per thread, the 16 threads in a fixed (xor butterfly) order
+__device__ __forceinline__ float sum16(float v) {
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  v += __shfl_xor(v, 4, 64);
+  v += __shfl_xor(v, 8, 64);
+  return v;
 }
 
 }  // namespace handoff

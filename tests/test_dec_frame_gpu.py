@@ -106,3 +106,40 @@ def test_dec_frame_sampled_matches_launch_path_and_oracle(top_k, dtype):
     del model
 
 
+
+
+def test_dec_frame_top_k_1_equals_greedy():
+    """Temperature 0.8 with top_k = 1 keeps the maximum alone, whatever the noise: the radix select runs all
+    four passes with one key left to find, and the Gumbel pass and the block arg-max see one candidate.  B = 1
+    bf16 on the persistent frame decoder, 4 frames: codes equal to the same engine's greedy codes and to the
+    oracle's.  No head of these frames has its two largest logits equal (asserted on the oracle's logits), so
+    a threshold off by one entry cannot hide behind a tie."""
+    from csm_mlx import _lib
+    from csm_mlx.generation import generate_codes_batch
+    from csm_mlx.models import CSM
+    from csm_mlx.sampling import Sampler
+    from csm_mlx.tokenizers import tokenize_text_segment
+    args, w = csm_weights("1b")
+    model = CSM(args, dtype="bf16")
+    model.load_weights(w)
+    L = _lib.lib()
+    prompt, frames = tokenize_text_segment(prompt_ids(31), 0, 32), 4
+    orc, logs = oracle_for(args, w, bf16=True).generate_codes(*prompt, frames, collect_logits=True)
+    for c0, ci in logs:
+        for row in (c0, *ci):
+            top = np.sort(row)[-2:]
+            assert top[1] > top[0], "two equal maxima: pick another prompt"
+    _lib.check(L.csm_set_option(model.engine, b"dec_frame", 1))
+
+    def run(smp):
+        ep0, ep1 = np.zeros(1, np.uint32), np.zeros(1, np.uint32)
+        _lib.check(L.csm_debug_read(model.engine, b"dec_frame_epoch", _lib.ptr(ep0), 4, None))
+        h, n, _ = generate_codes_batch(model, [prompt], frames, sampler=smp, seeds=[777])
+        _lib.check(L.csm_debug_read(model.engine, b"dec_frame_epoch", _lib.ptr(ep1), 4, None))
+        assert int(ep1[0]) - int(ep0[0]) == frames * 498, "the persistent frame decoder did not run every frame"
+        return h[: n[0], 0].copy()
+    greedy, got = run(Sampler(0.0, 0)), run(Sampler(0.8, 1))
+    del model
+    assert len(got) == frames and first_divergence(got, greedy) is None, \
+        f"top_k 1 differs from greedy at frame {first_divergence(got, greedy)}"
+    assert first_divergence(got, orc) is None, f"top_k 1 differs from the oracle's greedy codes at frame {first_divergence(got, orc)}"

@@ -194,3 +194,41 @@ def test_dec_xsd_in_launch_sampler_matches_sample_kernel(model_1b_q4, B):
     for b in range(B):
         d = first_divergence(got[0][: got[1][b], b], ref[0][: ref[1][b], b])
         assert d is None, f"utterance {b}: in-launch sampled codes differ at frame {d}"
+
+
+def test_dec_xsd_in_launch_sampler_top_k_1_equals_greedy(model_1b_q4):
+    """Temperature 0.8 with top_k = 1 through the sampler inside the step's launch (role_s): the maximum alone
+    is kept whatever the noise, so the radix select runs all four passes with one key left to find.  B = 8
+    int4 rows, 4 frames: codes equal to the same engine's greedy codes and to the oracle's.  No head of these
+    rows and frames has its two largest logits equal (asserted on the oracle's logits)."""
+    from csm_mlx import _lib
+    from csm_mlx.sampling import Sampler
+    from csm_mlx.tokenizers import tokenize_text_segment
+    args, w, model = model_1b_q4
+    L = _lib.lib()
+    B, frames = 8, 4
+    prompts = [tokenize_text_segment(prompt_ids(800 + b, 10 + b % 3), 0, args.n_audio_codebooks) for b in range(B)]
+    ref = oracle_batch(oracle_for(args, w, q4=True), prompts, frames, collect_logits=True)
+    for codes, logs in ref:
+        assert len(codes) == frames
+        for c0, ci in logs:
+            for row in (c0, *ci):
+                top = np.sort(row)[-2:]
+                assert top[1] > top[0], "two equal maxima: pick other prompts"
+    _lib.check(L.csm_set_option(model.engine, b"dec_xsd", 1))
+    _lib.check(L.csm_set_option(model.engine, b"dec_xsd_sample", 1))
+    K = model.n_audio_codebooks
+
+    def run(smp):
+        e0 = _epoch(model)
+        h, n, _ = _run(model, prompts, frames, smp)
+        assert _epoch(model) - e0 == frames * (K - 2), "the persistent step did not run every codebook step >= 2"
+        return h, n
+    (gh, gn), (sh, sn) = run(Sampler(0.0, 0)), run(Sampler(0.8, 1))
+    _lib.check(L.csm_synchronize(model.engine))
+    for b in range(B):
+        assert gn[b] == frames and sn[b] == frames
+        d = first_divergence(sh[:frames, b], gh[:frames, b])
+        assert d is None, f"utterance {b}: top_k 1 differs from greedy at frame {d}"
+        d = first_divergence(sh[:frames, b], ref[b][0])
+        assert d is None, f"utterance {b}: top_k 1 differs from the oracle's greedy codes at frame {d}"

@@ -116,3 +116,67 @@ def test_filter_boundaries_on_tied_rows(flt):
             assert int(hist[f, b, 0]) == exp, f"{flt}: utterance {b} frame {f}: GPU c0 {hist[f, b, 0]} vs oracle {exp}"
             checked += 1
     assert checked >= B * 2
+
+
+def _topk_tie_row(rng, V, n_above, n_tied):
+    """n_above distinct values above a tie of n_tied at the top-k boundary value, the rest (entry 0 among
+    it: c0 = 0 can never be picked, so no frame is an all-zero EOS frame) from a small set below."""
+    row = np.float32(rng.choice([0.0, 0.5, 1.0, 1.5], V))
+    idx = 1 + rng.choice(V - 1, n_above + n_tied, replace=False)
+    row[idx[:n_above]] = np.float32(3.0) + np.float32(0.25) * np.arange(1, n_above + 1, dtype=np.float32)
+    row[idx[n_above:]] = np.float32(3.0)
+    return row
+
+
+def _check_plain_topk(args, dtype, B, frames, shapes, prompts):
+    """Top-k only (sample_kernel, not the filtered kernel) on synthetic c0 rows: utterance b's row of frame f
+    has shapes[b] = (values above the tie, width of the tie at the 5th value); every frame's c0 against the
+    oracle's sample_one, no frame skipped."""
+    from csm_mlx.generation import generate_codes_batch
+    from csm_mlx.models import CSM
+    from csm_mlx.sampling import make_sampler
+    from oracle.csm_oracle import sample_one
+    _, w = csm_weights("tiny" if dtype == "float32" else "1b")
+    K, V = args.n_audio_codebooks, args.n_audio_vocab
+    model = CSM(args, dtype=dtype, max_batch=B)
+    model.load_weights(w)
+    rows = {}
+
+    def proc(hist, logits):
+        f = 0 if hist.size == 0 else hist.shape[0]
+        rng = np.random.default_rng(8100 + 37 * f)
+        rows[f] = np.stack([_topk_tie_row(rng, V, *shapes[b]) for b in range(B)])
+        return rows[f].copy()
+
+    smp = make_sampler(0.8, top_k=5)
+    assert not smp.filtered, "plain top-k: sample_kernel"
+    seeds = [5151 + 13 * b for b in range(B)]
+    hist, n, _ = generate_codes_batch(model, prompts, frames, sampler=smp, seeds=seeds, logits_processors=[proc])
+    del model
+    for b in range(B):
+        assert int(n[b]) == frames, f"utterance {b} ran {n[b]} of {frames} frames"
+        for f in range(frames):
+            kept = int((rows[f][b] >= np.float32(3.0)).sum())
+            assert kept == sum(shapes[b]), "the row is not what the case describes"
+            exp = sample_one(rows[f][b], 0.8, 5, seeds[b], f * K)
+            assert int(hist[f, b, 0]) == exp, f"utterance {b} frame {f} ({kept} kept): GPU c0 {hist[f, b, 0]} vs oracle {exp}"
+
+
+def test_plain_topk_ties_tiny():
+    """V = 67: one slot per thread, 189 of sample_kernel's 256 threads hold no entry.  top_k = 5 with a
+    5-way tie straddling the 5th value (3 above it): all 8 are kept."""
+    from csm_mlx.tokenizers import tokenize_text_segment
+    args, _ = csm_weights("tiny")
+    prompts = [tokenize_text_segment(tiny_prompt_ids(90 + b, 3 + b), 0, args.n_audio_codebooks) for b in range(2)]
+    _check_plain_topk(args, "float32", 2, 4, [(3, 5), (3, 5)], prompts)
+
+
+def test_plain_topk_ties_csm_1b():
+    """V = 2051: slot 8 of the 256 threads holds 3 valid entries.  top_k = 5, B = 2, 3 frames: utterance 0
+    keeps 10 entries (a 7-way tie at the 5th value: the LDS compaction), utterance 1 keeps 604 (a 600-way
+    tie: more than the compaction holds, the in-place loop).  A sampler that dropped ties would pick among
+    5; the oracle's pick lies in the 600-way tie (for 40 of 40 seeds tried on the CPU)."""
+    from csm_mlx.tokenizers import tokenize_text_segment
+    args, _ = csm_weights("1b")
+    prompts = [tokenize_text_segment(prompt_ids(70 + b, 10), 0, 32) for b in range(2)]
+    _check_plain_topk(args, "bf16", 2, 3, [(3, 7), (4, 600)], prompts)
