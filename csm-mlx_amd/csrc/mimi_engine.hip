@@ -88,8 +88,6 @@ struct mimi_codec {
   size_t r_rows = 0;  // rows of R the last call left (mimi_debug_read "rows")
   int* dcodes = nullptr;
   size_t dcodes_n = 0;
-  float* dpcm = nullptr;
-  size_t dpcm_n = 0;
   // transformer KV (encoder one-shot; decoder one-shot + streaming)
   std::vector<float*> ekc, evc, dkc, dvc;
   // streaming state
@@ -108,7 +106,7 @@ struct mimi_codec {
   }
   ~mimi_codec() {
     for (void* p : allocs) (void)hipFree(p);
-    for (float* p : {W0, W1, H, E, R, Rh, Rqkv, Rq, Ratt, Rf, dpcm}) if (p) (void)hipFree(p);
+    for (float* p : {W0, W1, H, E, R, Rh, Rqkv, Rq, Ratt, Rf}) if (p) (void)hipFree(p);
     if (dcodes) (void)hipFree(dcodes);
     if (rvq_r) (void)hipFree(rvq_r);
     if (rvq_p) (void)hipFree(rvq_p);
@@ -283,28 +281,49 @@ void grow(T*& p, size_t& cap, size_t n) {
 }
 
 void ensure_ws(mimi_codec* m, size_t big, size_t rows_M) {
+  // (the buffers of a group grow together, on the group's one capacity: each from a capacity of 0)
+  auto regrow = [](float*& p, size_t n) {
+    size_t none = 0;
+    grow(p, none, n);
+  };
   if (big > m->ws_big) {
-    for (float** p : {&m->W0, &m->W1, &m->H, &m->E})
-      if (*p) (void)hipFree(*p);
-    for (float** p : {&m->W0, &m->W1, &m->H, &m->E})
-      if (hipMalloc((void**)p, big * 4) != hipSuccess) throw CsmError(CSM_ERR_HIP, "workspace allocation failed");
+    for (float** p : {&m->W0, &m->W1, &m->H, &m->E}) regrow(*p, big);
     m->ws_big = big;
   }
   if (rows_M > m->ws_rows) {
     const size_t D = m->d.dimension, F = m->d.dim_feedforward;
-    for (float** p : {&m->R, &m->Rh, &m->Rqkv, &m->Rq, &m->Ratt, &m->Rf})
-      if (*p) (void)hipFree(*p);
-    auto A = [&](float** p, size_t n) {
-      if (hipMalloc((void**)p, n * 4) != hipSuccess) throw CsmError(CSM_ERR_HIP, "workspace allocation failed");
-    };
-    A(&m->R, rows_M * D);
-    A(&m->Rh, rows_M * std::max(D, (size_t)m->d.codebook_dim));
-    A(&m->Rqkv, rows_M * 3 * D);
-    A(&m->Rq, rows_M * D);
-    A(&m->Ratt, rows_M * D);
-    A(&m->Rf, rows_M * F);
+    const std::pair<float**, size_t> rows[] = {{&m->R, D},  {&m->Rh, std::max(D, (size_t)m->d.codebook_dim)},
+                                               {&m->Rqkv, 3 * D}, {&m->Rq, D}, {&m->Ratt, D}, {&m->Rf, F}};
+    for (const auto& r : rows) regrow(*r.first, rows_M * r.second);
     m->ws_rows = rows_M;
   }
+}
+
+// An activation tensor in conv layout: channel rows cs floats apart, sample 0 at off of each row, len
+// samples; utterances are (channels of the op that reads or writes it) * cs apart.
+struct Act {
+  float* p;
+  int cs, off, len;
+};
+
+// The causal conv c from `in` to the out.len steps of `out`, left-padded by pad_l (zeros, or the edge sample)
+ConvParams conv_params(mimi_codec* m, const MConv& c, Act in, Act out, int B, int pad_l, bool replicate = false) {
+  ConvParams p{};
+  p.ks_ws = m->ks_ws;
+  p.x = in.p; p.Cin = c.cin; p.Tin = in.len; p.x_bstride = c.cin * in.cs; p.x_cstride = in.cs; p.x_off = in.off;
+  p.w = c.w; p.bias = c.b; p.Cout = c.cout; p.k = c.k; p.stride = c.stride; p.dil = c.dil; p.pad_l = pad_l;
+  p.replicate = replicate; p.elu_in = c.elu;
+  p.y = out.p; p.Tout = out.len; p.y_bstride = c.cout * out.cs; p.y_cstride = out.cs; p.y_off = out.off; p.B = B;
+  return p;
+}
+
+// out = epi(x [M][K] . W [N][K]^T), both row-major and dense
+LinParams lin_params(mimi_codec* m, const float* x, int M, int K, const float* W, int N, float* out,
+                     int epi = EPI_STORE, const float* scale = nullptr) {
+  LinParams lp{};
+  lp.ks_ws = m->ks_ws;
+  lp.x = x; lp.M = M; lp.K = K; lp.xs = K; lp.W = W; lp.N = N; lp.out = out; lp.os = N; lp.epi = epi; lp.scale = scale;
+  return lp;
 }
 
 // x rows [M = B*T][D] in place through the codec transformer; positions offset..offset+T-1
@@ -317,33 +336,19 @@ void run_transformer(mimi_codec* m, std::vector<MTLayer>& T, std::vector<float*>
   for (size_t l = 0; l < T.size(); ++l) {
     MTLayer& L = T[l];
     launch_layernorm_rows(m->R, D, L.n1w, L.n1b, d.norm_eps, m->Rh, M, st);
-    LinParams lp{};
-    lp.ks_ws = m->ks_ws;
-    lp.x = m->Rh; lp.M = M; lp.K = D; lp.xs = D; lp.W = L.in_w; lp.N = 3 * D; lp.out = m->Rqkv; lp.os = 3 * D;
-    lp.epi = EPI_STORE;
-    launch_linear(lp, st);
+    launch_linear(lin_params(m, m->Rh, M, D, L.in_w, 3 * D, m->Rqkv), st);
     launch_rope_append(m->Rqkv, M, D, H, hd, m->rope, rm, m->Rq, kc[l], vc[l], m->S_cap, st);
     AttnParams a{};
     a.q = m->Rq; a.qs = D; a.M = M; a.kc = kc[l]; a.vc = vc[l]; a.Hq = H; a.Hkv = H; a.S_cap = m->S_cap;
     a.scale = 1.0f / sqrtf((float)hd); a.window = d.context; a.rm = rm; a.out = m->Ratt; a.os = D;
     a.mode = d.attn_mode == 0 ? ATTN_BLOCK : ATTN_WINDOW;
     launch_attn(a, hd, st);
-    lp = LinParams{};
-    lp.ks_ws = m->ks_ws;
-    lp.x = m->Ratt; lp.M = M; lp.K = D; lp.xs = D; lp.W = L.out_w; lp.N = D; lp.out = m->R; lp.os = D;
-    lp.epi = EPI_ADD; lp.scale = L.ls1;
-    launch_linear(lp, st);
+    launch_linear(lin_params(m, m->Ratt, M, D, L.out_w, D, m->R, EPI_ADD, L.ls1), st);
     launch_layernorm_rows(m->R, D, L.n2w, L.n2b, d.norm_eps, m->Rh, M, st);
-    lp = LinParams{};
-    lp.ks_ws = m->ks_ws;
-    lp.x = m->Rh; lp.M = M; lp.K = D; lp.xs = D; lp.W = L.l1; lp.N = F; lp.out = m->Rf; lp.os = F;
-    lp.epi = EPI_GELU; lp.gelu_erf = d.gelu_erf;
-    launch_linear(lp, st);
-    lp = LinParams{};
-    lp.ks_ws = m->ks_ws;
-    lp.x = m->Rf; lp.M = M; lp.K = F; lp.xs = F; lp.W = L.l2; lp.N = D; lp.out = m->R; lp.os = D;
-    lp.epi = EPI_ADD; lp.scale = L.ls2;
-    launch_linear(lp, st);
+    LinParams up = lin_params(m, m->Rh, M, D, L.l1, F, m->Rf, EPI_GELU);
+    up.gelu_erf = d.gelu_erf;
+    launch_linear(up, st);
+    launch_linear(lin_params(m, m->Rf, M, F, L.l2, D, m->R, EPI_ADD, L.ls2), st);
   }
 }
 
@@ -361,47 +366,50 @@ bool mimi_elu_pre() {
   return v;
 }
 
-// One decoder-SEANet op on a window buffer: input window [B][cin][P + n] in `in` (channel stride
-// cs_in), output [B][cout][P' + n'] written at offset P' (the next op's history length) of `out`.
+// How an op stores its output for the ELU of the op after it: ELU(y) in place of y, or ELU(y) to y2 beside y
+struct EluOut {
+  int elu_out = 0;
+  float* y2 = nullptr;
+};
+
+// A residual block: ELU -> conv(k, ch -> hid) into m->H -> ELU -> conv(1, hid -> ch) + identity skip
+// (true_skip).  x1 is what block.1 reads, left-padded by pad_l (x1_elu: it already holds ELU(x)); skip is the
+// block's input at the output steps.  H feeds only block.3's ELU, so it holds ELU(h) unless CSM_MIMI_ELU_PRE=0.
+void run_res(mimi_codec* m, const MRes& r, Act x1, bool x1_elu, int pad_l, Act skip, Act out, int B, EluOut eo) {
+  const Act h{m->H, out.len, 0, out.len};
+  ConvParams p = conv_params(m, r.c1, x1, h, B, pad_l);
+  p.elu_in = !x1_elu;
+  p.elu_out = mimi_elu_pre();
+  launch_conv1d(p, m->st);
+  ConvParams q = conv_params(m, r.c2, h, out, B, 0);
+  q.elu_in = !mimi_elu_pre();
+  q.resid = skip.p; q.r_bstride = r.ch * skip.cs; q.r_cstride = skip.cs; q.r_off = skip.off;
+  q.elu_out = eo.elu_out; q.y2 = eo.y2;
+  launch_conv1d(q, m->st);
+}
+
+// One decoder-SEANet op on a window buffer: input window `in` = [P history | n new] samples per channel,
+// output written behind the next op's history (out.off) of `out`.
 // in_elu: the window holds ELU(x) (its producer stored it so); out_elu: store ELU(y) for an ELU-input
 // next op (histories copy whichever the window holds, so the two stay consistent from call to call)
-void run_window_op(mimi_codec* m, const MOp& o, const float* in, int cs_in, int P, int n, float* out, int cs_out,
-                   int P_next, int B, bool in_elu = false, bool out_elu = false) {
-  hipStream_t st = m->st;
+void run_window_op(mimi_codec* m, const MOp& o, Act in, int P, Act out, int B, bool in_elu, bool out_elu) {
   if (o.kind == 0) {
     const MConv& c = m->convs[o.idx];
-    ConvParams p{};
-    p.ks_ws = m->ks_ws;
-    p.x = in; p.Cin = c.cin; p.Tin = P + n; p.x_bstride = c.cin * cs_in; p.x_cstride = cs_in; p.x_off = 0;
-    p.w = c.w; p.bias = c.b; p.Cout = c.cout; p.k = c.k; p.stride = 1; p.dil = c.dil; p.pad_l = 0;
-    p.replicate = 0; p.elu_in = c.elu && !in_elu; p.y = out; p.Tout = n; p.y_bstride = c.cout * cs_out; p.y_cstride = cs_out;
-    p.y_off = P_next; p.B = B; p.elu_out = out_elu;
-    launch_conv1d(p, st);
+    ConvParams p = conv_params(m, c, in, out, B, 0);
+    p.elu_in = c.elu && !in_elu;
+    p.elu_out = out_elu;
+    launch_conv1d(p, m->st);
   } else if (o.kind == 1) {
     const MConvTr& t = m->convtrs[o.idx];
     ConvTrParams p{};
     p.ks_ws = m->ks_ws;
-    p.x = in; p.Cin = t.cin; p.Tin = P + n; p.x_bstride = t.cin * cs_in; p.x_cstride = cs_in; p.x_off = 0;
-    p.wt = t.wt; p.bias = t.b; p.Cout = t.cout; p.s = t.s; p.elu_in = t.elu && !in_elu; p.t_in0 = P; p.n_in = n; p.y = out;
-    p.y_bstride = t.cout * cs_out; p.y_cstride = cs_out; p.y_off = P_next; p.B = B;
-    launch_convtr(p, st);
+    p.x = in.p; p.Cin = t.cin; p.Tin = in.len; p.x_bstride = t.cin * in.cs; p.x_cstride = in.cs; p.x_off = in.off;
+    p.wt = t.wt; p.bias = t.b; p.Cout = t.cout; p.s = t.s; p.elu_in = t.elu && !in_elu; p.t_in0 = P; p.n_in = in.len - P;
+    p.y = out.p; p.y_bstride = t.cout * out.cs; p.y_cstride = out.cs; p.y_off = out.off; p.B = B;
+    launch_convtr(p, m->st);
   } else {
-    const MRes& r = m->res[o.idx];
-    ConvParams p{};
-    p.ks_ws = m->ks_ws;  // block.1: ELU -> conv(k, ch -> hid) over the window
-    p.x = in; p.Cin = r.ch; p.Tin = P + n; p.x_bstride = r.ch * cs_in; p.x_cstride = cs_in; p.x_off = 0;
-    p.w = r.c1.w; p.bias = r.c1.b; p.Cout = r.hid; p.k = r.k; p.stride = 1; p.dil = r.dil; p.pad_l = 0;
-    p.elu_in = 1; p.y = m->H; p.Tout = n; p.y_bstride = r.hid * n; p.y_cstride = n; p.y_off = 0; p.B = B;
-    p.elu_out = mimi_elu_pre();  // H feeds only block.3's ELU
-    launch_conv1d(p, st);
-    ConvParams q{};
-    q.ks_ws = m->ks_ws;  // block.3: ELU -> conv(1, hid -> ch) + identity skip (true_skip)
-    q.x = m->H; q.Cin = r.hid; q.Tin = n; q.x_bstride = r.hid * n; q.x_cstride = n; q.x_off = 0;
-    q.w = r.c2.w; q.bias = r.c2.b; q.Cout = r.ch; q.k = 1; q.stride = 1; q.dil = 1; q.pad_l = 0;
-    q.elu_in = !mimi_elu_pre();
-    q.y = out; q.Tout = n; q.y_bstride = r.ch * cs_out; q.y_cstride = cs_out; q.y_off = P_next;
-    q.resid = in; q.r_bstride = r.ch * cs_in; q.r_cstride = cs_in; q.r_off = P; q.B = B; q.elu_out = out_elu;
-    launch_conv1d(q, st);
+    // block.1 reads the whole window; the skip is the window behind its history
+    run_res(m, m->res[o.idx], in, false, 0, Act{in.p, in.cs, in.off + P, out.len}, out, B, EluOut{out_elu, nullptr});
   }
 }
 
@@ -438,7 +446,7 @@ const float* run_decoder_seanet(mimi_codec* m, int B, int n_lat, bool use_hist) 
     // an output that only an ELU-input op reads is stored as ELU(y) (a transposed conv's output feeds a
     // residual block, whose skip needs y itself)
     const bool out_elu = mimi_elu_pre() && !last && o.kind != 1 && elu_input(ops[i + 1]);
-    run_window_op(m, o, in, cs_in, P, n, bufs[cur ^ 1], cs_out, P_next, B, in_elu, out_elu);
+    run_window_op(m, o, Act{in, cs_in, 0, cs_in}, P, Act{bufs[cur ^ 1], cs_out, P_next, n_out}, B, in_elu, out_elu);
     in_elu = out_elu;
     // window tail -> history for the next call
     if (use_hist && P > 0) launch_copy_window(in, B, cin, cin * cs_in, cs_in, n, m->hist[i], cin * P, P, 0, P, m->st);
@@ -458,6 +466,18 @@ size_t decoder_ws(mimi_codec* m, int n_lat) {  // max window elements per uttera
     best = std::max(best, (size_t)m->op_cout(o) * (n + 8));
   }
   return best;
+}
+
+// The PCM of n_lat latent steps after run_decoder_seanet: [B][1][n] in the ping-pong buffer it ended in
+struct Pcm {
+  const float* p;
+  int n;
+};
+Pcm decoder_pcm(const mimi_codec* m, int n_lat) {
+  int n = n_lat;
+  for (const MOp& o : m->dec_ops)
+    if (o.kind == 1) n *= m->convtrs[o.idx].s;
+  return Pcm{m->dec_ops.size() % 2 == 0 ? m->W0 : m->W1, n};
 }
 
 }  // namespace
@@ -480,9 +500,6 @@ int mimi_create(const mimi_dims* dims, int device, int max_batch, int max_frames
     m->hd = hd;
     m->B_max = max_batch;
     m->F_max = max_frames;
-    int hop = 1;
-    for (int i = 0; i < dims->n_ratios; ++i) hop *= dims->ratios[i];
-    (void)hop;
     m->S_cap = 2 * max_frames * dims->downsample_stride / 2 + 16;  // latent (25 Hz) positions
     m->S_cap = std::max(m->S_cap, 2 * max_frames + 16);
     // the codec's stream at the lowest priority (the engine's at the highest), so a streaming decode_step
@@ -617,59 +634,37 @@ int mimi_encode_rows(mimi_codec* m, int B, int N, const float* pcm, const float*
     // holds ELU(x); have_e: m->E holds ELU(bufs[cur]).
     const bool elu_pre = mimi_elu_pre();
     bool in_elu = false, have_e = false;
-    auto out_elu = [&](size_t i, ConvParams& p) {
+    auto out_elu = [&](size_t i) {
+      EluOut eo;
       const MOp* nx = i + 1 < m->enc_ops.size() ? &m->enc_ops[i + 1] : nullptr;
-      if (!elu_pre || !nx) return;
-      if (nx->kind == 0 && m->convs[nx->idx].elu) p.elu_out = 1;
-      else if (nx->kind != 0) p.y2 = m->E;
+      if (!elu_pre || !nx) return eo;
+      if (nx->kind == 0 && m->convs[nx->idx].elu) eo.elu_out = 1;
+      else if (nx->kind != 0) eo.y2 = m->E;
+      return eo;
     };
+    auto full = [](float* p, int64_t T) { return Act{p, (int)T, 0, (int)T}; };  // a whole sequence, dense
     for (size_t i = 0; i < m->enc_ops.size(); ++i) {
       const MOp& o = m->enc_ops[i];
       float* in = bufs[cur];
       float* out = bufs[cur ^ 1];
-      bool nx_in_elu = false, nx_have_e = false;
+      const EluOut eo = out_elu(i);
       if (o.kind == 0) {
         const MConv& c = m->convs[o.idx];
         const int k_eff = (c.k - 1) * c.dil + 1;
         const int64_t Tout = lens[i + 1];
-        ConvParams p{};
-        p.ks_ws = m->ks_ws;
-        p.x = in; p.Cin = c.cin; p.Tin = (int)Tin; p.x_bstride = c.cin * (int)Tin; p.x_cstride = (int)Tin;
-        p.w = c.w; p.bias = c.b; p.Cout = c.cout; p.k = c.k; p.stride = c.stride; p.dil = c.dil;
-        p.pad_l = k_eff - c.stride; p.elu_in = c.elu; p.y = out; p.Tout = (int)Tout;
-        p.y_bstride = c.cout * (int)Tout; p.y_cstride = (int)Tout; p.B = B;
+        ConvParams p = conv_params(m, c, full(in, Tin), full(out, Tout), B, k_eff - c.stride);
         if (in_elu && !c.elu) throw CsmError(CSM_ERR_HIP, "mimi encoder: ELU bookkeeping");
         if (in_elu) p.elu_in = 0;
-        out_elu(i, p);
-        nx_in_elu = p.elu_out != 0;
-        nx_have_e = p.y2 != nullptr;
+        p.elu_out = eo.elu_out; p.y2 = eo.y2;
         launch_conv1d(p, st);
         Tin = Tout;
-      } else {  // resblock on the full sequence (causal, zero left pad)
+      } else {  // resblock on the full sequence (causal, zero left pad); block.1 reads m->E when it holds ELU(in)
         const MRes& r = m->res[o.idx];
-        ConvParams p{};
-        p.ks_ws = m->ks_ws;
-        p.x = in; p.Cin = r.ch; p.Tin = (int)Tin; p.x_bstride = r.ch * (int)Tin; p.x_cstride = (int)Tin;
-        p.w = r.c1.w; p.bias = r.c1.b; p.Cout = r.hid; p.k = r.k; p.stride = 1; p.dil = r.dil;
-        p.pad_l = (r.k - 1) * r.dil; p.elu_in = 1; p.y = m->H; p.Tout = (int)Tin; p.y_bstride = r.hid * (int)Tin;
-        p.y_cstride = (int)Tin; p.B = B;
         if (in_elu) throw CsmError(CSM_ERR_HIP, "mimi encoder: ELU bookkeeping");
-        if (have_e) { p.x = m->E; p.elu_in = 0; }
-        p.elu_out = elu_pre;  // H feeds only the block's second (ELU-input) conv
-        launch_conv1d(p, st);
-        ConvParams q{};
-        q.ks_ws = m->ks_ws;
-        q.x = m->H; q.Cin = r.hid; q.Tin = (int)Tin; q.x_bstride = r.hid * (int)Tin; q.x_cstride = (int)Tin;
-        q.w = r.c2.w; q.bias = r.c2.b; q.Cout = r.ch; q.k = 1; q.stride = 1; q.dil = 1; q.elu_in = elu_pre ? 0 : 1; q.y = out;
-        q.Tout = (int)Tin; q.y_bstride = r.ch * (int)Tin; q.y_cstride = (int)Tin; q.resid = in;
-        q.r_bstride = r.ch * (int)Tin; q.r_cstride = (int)Tin; q.B = B;
-        out_elu(i, q);
-        nx_in_elu = q.elu_out != 0;
-        nx_have_e = q.y2 != nullptr;
-        launch_conv1d(q, st);
+        run_res(m, r, full(have_e ? m->E : in, Tin), have_e, (r.k - 1) * r.dil, full(in, Tin), full(out, Tin), B, eo);
       }
-      in_elu = nx_in_elu;
-      have_e = nx_have_e;
+      in_elu = eo.elu_out != 0;
+      have_e = eo.y2 != nullptr;
       cur ^= 1;
     }
     // transformer on [B][dim][T25]
@@ -679,26 +674,16 @@ int mimi_encode_rows(mimi_codec* m, int B, int N, const float* pcm, const float*
     launch_rows_to_conv(m->R, B, D, (int)T25, bufs[cur ^ 1], D * (int)T25, (int)T25, 0, st);
     cur ^= 1;
     // downsample: k = 2s, stride s, replicate pad, no bias
-    {
-      ConvParams p{};
-      p.ks_ws = m->ks_ws;
-      p.x = bufs[cur]; p.Cin = D; p.Tin = (int)T25; p.x_bstride = D * (int)T25; p.x_cstride = (int)T25;
-      p.w = m->down_w; p.Cout = D; p.k = 2 * s; p.stride = s; p.dil = 1; p.pad_l = s; p.replicate = 1;
-      p.y = bufs[cur ^ 1]; p.Tout = (int)Tf; p.y_bstride = D * (int)Tf; p.y_cstride = (int)Tf; p.B = B;
-      launch_conv1d(p, st);
-      cur ^= 1;
-    }
+    const MConv down{D, D, 2 * s, s, 1, 0, m->down_w, nullptr};
+    launch_conv1d(conv_params(m, down, full(bufs[cur], T25), full(bufs[cur ^ 1], Tf), B, s, true), st);
+    cur ^= 1;
     // split RVQ: semantic and acoustic both quantize the same latent
     launch_conv_to_rows(bufs[cur], B, D, (int)Tf, D * (int)Tf, (int)Tf, 0, m->R, st);
     const int M = B * (int)Tf, cd = d.codebook_dim;
     m->r_rows = (size_t)M;  // R: the pre-RVQ latent, read only from here on
     grow(m->dcodes, m->dcodes_n, (size_t)B * d.n_q * Tf);
     for (int q = 0; q < 2; ++q) {
-      LinParams lp{};
-      lp.ks_ws = m->ks_ws;
-      lp.x = m->R; lp.M = M; lp.K = D; lp.xs = D; lp.W = m->rvq_in[q]; lp.N = cd; lp.out = m->Rh; lp.os = cd;
-      lp.epi = EPI_STORE;
-      launch_linear(lp, st);
+      launch_linear(lin_params(m, m->R, M, D, m->rvq_in[q], cd, m->Rh), st);
       const int k0 = q == 0 ? 0 : 1, k1 = q == 0 ? 1 : d.n_q;
       if (k1 <= k0) continue;
       // many rows: one distance GEMM launch per codebook (profiles/r04_ab_rvq_gemm.txt), else a block per row
@@ -727,10 +712,8 @@ static void decode_frames(mimi_codec* m, int B, int F, const int32_t* dcodes, in
   const int M = B * F;
   // RVQ decode: semantic + acoustic gathers, output projections summed into conv layout [B][D][F]
   launch_rvq_gather(dcodes, layout, B, F, d.n_q, 0, 1, m->cb, d.bins, cd, m->Rh, st);
-  LinParams lp{};
-  lp.ks_ws = m->ks_ws;
-  lp.x = m->Rh; lp.M = M; lp.K = cd; lp.xs = cd; lp.W = m->rvq_out[0]; lp.N = D; lp.conv_T = F;
-  lp.conv_bstride = D * F; lp.out = m->W1; lp.accumulate = 0;
+  LinParams lp = lin_params(m, m->Rh, M, cd, m->rvq_out[0], D, m->W1);
+  lp.conv_T = F; lp.conv_bstride = D * F;
   launch_linear(lp, st);
   if (d.n_q > 1) {
     launch_rvq_gather(dcodes, layout, B, F, d.n_q, 1, d.n_q, m->cb, d.bins, cd, m->Rh, st);
@@ -778,14 +761,9 @@ int mimi_decode(mimi_codec* m, int B, int F, const int32_t* codes, int codes_on_
     }
     decode_frames(m, B, F, dc, codes_layout, false);
     m->s_off = 0;
-    // final window: [B][1][F*frame] in whichever ping-pong buffer run_decoder_seanet ended in
-    const int n_out = F * s;
-    int n = n_out;
-    for (const MOp& o : m->dec_ops)
-      if (o.kind == 1) n *= m->convtrs[o.idx].s;
-    const float* src = (m->dec_ops.size() % 2 == 0) ? m->W0 : m->W1;
-    const size_t bytes = (size_t)B * n * 4;
-    HIPCHK(hipMemcpyAsync(pcm, src, bytes, pcm_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, m->st));
+    const Pcm out = decoder_pcm(m, F * s);
+    HIPCHK(hipMemcpyAsync(pcm, out.p, (size_t)B * out.n * 4,
+                          pcm_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, m->st));
     HIPCHK(hipStreamSynchronize(m->st));
     HIPCHK(hipGetLastError());
   }
@@ -818,11 +796,8 @@ int mimi_decode_step(mimi_codec* m, int B, const int32_t* codes, float* pcm) {
     grow(m->dcodes, m->dcodes_n, (size_t)B * m->d.n_q);
     HIPCHK(hipMemcpyAsync(m->dcodes, codes, (size_t)B * m->d.n_q * 4, hipMemcpyHostToDevice, m->st));
     decode_frames(m, B, 1, m->dcodes, 0, true);
-    int n = s;
-    for (const MOp& o : m->dec_ops)
-      if (o.kind == 1) n *= m->convtrs[o.idx].s;
-    const float* src = (m->dec_ops.size() % 2 == 0) ? m->W0 : m->W1;
-    HIPCHK(hipMemcpyAsync(pcm, src, (size_t)B * n * 4, hipMemcpyDeviceToHost, m->st));
+    const Pcm out = decoder_pcm(m, s);
+    HIPCHK(hipMemcpyAsync(pcm, out.p, (size_t)B * out.n * 4, hipMemcpyDeviceToHost, m->st));
     HIPCHK(hipStreamSynchronize(m->st));
     HIPCHK(hipGetLastError());
   }

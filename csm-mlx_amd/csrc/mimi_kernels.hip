@@ -6,6 +6,10 @@
 // Everything stays fp32 (waveform parity target: 1e-4 RMS).
 #include "mimi_kernels.h"
 
+#include <string>
+
+#include "engine_util.h"
+
 // ============================================================================ tiled GEMM core
 // Four consecutive floats at p as one 16-B load when p is 16-B aligned (else four 4-B loads): the
 // same values either way, fewer load instructions for the tile staging.
@@ -19,135 +23,36 @@ __device__ __forceinline__ void ld4(const float* p, float (&v)[4]) {
   }
 }
 
-// out(i, j) = sum_kk A(i, kk) * B(kk, j); 64 x 64 tile, K-step 16, on the matrix cores.
+// out(i, j) = sum_kk A(i, kk) * B(kk, j); BM x BN tile, K-step 16, on the matrix cores.
 // Problems supply a(), b(), their 4-wide forms aptr() / b4() / b4k(), the epilogue pre() / post() and
 // store(); B_KCONTIG / kcontig() select the B-tile load mapping (consecutive kk per thread when B's
 // memory is contiguous along kk, else consecutive j).
+// Tiles: 64 x 64, and for wide problems (>= 256 columns: whole-utterance encode / decode convs, the codec
+// transformer's linears) BM x 128 with BM 128, or 64 / 32 for the 64- / 32-channel convs, which a taller
+// tile ran padded.  The four waves sit 2 x 2 (1 x 4 at BM 32), each on a (BM / WM) x (BN / WN) block of
+// TM x TN MFMA tiles of 32 x 32 (128 x 128: 2 x 2 per wave, one A and one B LDS dword per two MFMAs
+// instead of per one).
 // SPLIT: blockIdx.z = z * ks + slice; the block sums K range [slice * KD / ks, (slice + 1) * KD / ks)
 // (whole 16-steps) and writes its raw tile to slab[slice][z][i][j]; splitk_reduce_kernel adds the slices
 // in order and runs the problem's epilogue.
 // v_mfma_f32_32x32x2_f32 (fp32 operands, fp32 accumulation) adds its two products in k order with a
-// rounding after each (MI355X_MICROARCH.md, f32-input MFMA "exact f32 (= fmaf chain, bitwise)"), so
-// every output is one fmaf chain over kk in order, bit for bit what the VALU tile this replaced gave
-// (profiles/r04_ab_mimi_mfma.txt).
-// Wave w owns the 32 x 32 quadrant (w >> 1, w & 1): per K-step 8 MFMAs, operands one LDS dword per
-// lane (lane (r, h): A(i0 + 32 qi + r, k0 + 2t + h), B(k0 + 2t + h, j0 + 32 qj + r)); accumulator register
-// q of lane (r, h) holds output row 8 (q >> 2) + 4 h + (q & 3) of the quadrant, column r.  The next K tile
-// is fetched into registers while the current one is multiplied (one tile of prefetch hides the
-// global-load latency that a load -> sync -> compute loop exposes per step); the im2col staging's VALU
-// work for the next K-step runs beside the MFMAs.
-template <class P, bool SPLIT>
-__global__ __launch_bounds__(256) void gemm64_mf_kernel(P p, int ks, float* slab, int Z) {
+// rounding after each (MI355X_MICROARCH.md, f32-input MFMA "exact f32 (= fmaf chain, bitwise)"), and each
+// output has one accumulator fed k in order, so every output is one fmaf chain over kk in order whatever
+// the tile shape, bit for bit what the VALU tile this replaced gave (profiles/r04_ab_mimi_mfma.txt).
+// Per K-step 8 MFMAs per 32 x 32 tile, operands one LDS dword per lane (lane (r, h): A(row r of the tile,
+// k0 + 2t + h), B(k0 + 2t + h, column r)); accumulator register q of lane (r, h) holds output row
+// 8 (q >> 2) + 4 h + (q & 3) of the tile, column r.  LDS rows are BM + 32 / BN + 32 floats apart (BM when
+// BM % 64 == 32), so the two k rows an MFMA operand read touches (lanes h = 0 / 1) land on disjoint halves
+// of the 64 banks; the 64 x 64 tile keeps the 68 it was tuned at.  The next K tile is fetched into
+// registers while the current one is multiplied (one tile of prefetch hides the global-load latency that
+// a load -> sync -> compute loop exposes per step); the im2col staging's VALU work for the next K-step
+// runs beside the MFMAs.
+template <class P, bool SPLIT, int BM, int BN>
+__global__ __launch_bounds__(256) void gemm_mf_kernel(P p, int ks, float* slab, int Z) {
   typedef float f32x16_t __attribute__((ext_vector_type(16)));
-  __shared__ __attribute__((aligned(16))) float As[16][68];
-  __shared__ __attribute__((aligned(16))) float Bs[16][68];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, qi = wave >> 1, qj = wave & 1;
-  const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
-  const int z = SPLIT ? (int)blockIdx.z / ks : (int)blockIdx.z, sl = SPLIT ? (int)blockIdx.z % ks : 0;
-  const int KD = p.kdim();
-  int kb = 0, ke = KD;
-  if constexpr (SPLIT) {
-    const int nst = (KD + 15) / 16;
-    kb = (nst * sl / ks) * 16;
-    ke = min(KD, (nst * (sl + 1) / ks) * 16);
-  }
-  f32x16_t acc = {};
-  float va[4], vb[4];
-  // B staged along kk (runs of taps) for the linears and the strided convs, along the output steps
-  // otherwise
-  const bool bk = P::B_KCONTIG || p.kcontig();
-  // (whole runs of four inside the tile take the problem's 4-wide loads: A along kk, B along kk
-  // or along the output steps; the values are those of the per-element accessors)
-  auto fetch = [&](int k0) {
-    {
-      const int i = tid >> 2, kq = (tid & 3) * 4;
-      if (i0 + i < p.M && k0 + kq + 3 < ke) {
-        ld4(p.aptr(z, i0 + i, k0 + kq), va);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          va[e] = (i0 + i < p.M && k0 + kq + e < ke) ? p.a(z, i0 + i, k0 + kq + e) : 0.f;
-      }
-    }
-    if (bk) {
-      const int j = tid >> 2, kq = (tid & 3) * 4;
-      if (!(j0 + j < p.N && k0 + kq + 3 < ke && p.b4k(z, k0 + kq, j0 + j, vb))) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          vb[e] = (j0 + j < p.N && k0 + kq + e < ke) ? p.b(z, k0 + kq + e, j0 + j) : 0.f;
-      }
-    } else {
-      const int kk = tid >> 4, jb = (tid & 15) * 4;
-      if (!(k0 + kk < ke && j0 + jb + 3 < p.N && p.b4(z, k0 + kk, j0 + jb, vb))) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          vb[e] = (k0 + kk < ke && j0 + jb + e < p.N) ? p.b(z, k0 + kk, j0 + jb + e) : 0.f;
-      }
-    }
-  };
-  fetch(kb);
-  const int r = lane & 31, h = lane >> 5;
-  for (int k0 = kb; k0 < ke; k0 += 16) {
-    {
-      const int i = tid >> 2, kq = (tid & 3) * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) As[kq + e][i] = va[e];
-    }
-    if (bk) {
-      const int j = tid >> 2, kq = (tid & 3) * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) Bs[kq + e][j] = vb[e];
-    } else {
-      const int kk = tid >> 4, jb = (tid & 15) * 4;
-      *reinterpret_cast<float4*>(&Bs[kk][jb]) = make_float4(vb[0], vb[1], vb[2], vb[3]);
-    }
-    __syncthreads();
-    if (k0 + 16 < ke) fetch(k0 + 16);
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[2 * t + h][32 * qi + r], Bs[2 * t + h][32 * qj + r], acc, 0, 0, 0);
-    __syncthreads();
-  }
-  // the epilogue's loads (bias, residual, accumulated-onto values) issued four rows at a time before
-  // their stores (which they could alias as far as the compiler knows): 4 memory round trips per tile
-  // instead of 16
-  if constexpr (SPLIT) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int i = i0 + 32 * qi + 8 * (q >> 2) + 4 * h + (q & 3), j = j0 + 32 * qj + r;
-      if (i < p.M && j < p.N) slab[(((size_t)sl * Z + z) * p.M + i) * p.N + j] = acc[q];
-    }
-  } else {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {  // four rows at a time (registers: occupancy of the main loop)
-      float2 e[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int i = i0 + 32 * qi + 8 * g + 4 * h + u, j = j0 + 32 * qj + r;
-        e[u] = (i < p.M && j < p.N) ? p.pre(z, i, j) : make_float2(0.f, 0.f);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int i = i0 + 32 * qi + 8 * g + 4 * h + u, j = j0 + 32 * qj + r;
-        if (i < p.M && j < p.N) p.post(z, i, j, acc[4 * g + u], e[u]);
-      }
-    }
-  }
-}
-
-// Wide problems (>= 256 columns: whole-utterance encode / decode convs, the codec transformer's
-// linears): BM x 128 tiles, each wave a (BM / WM) x (128 / WN) block of 32 x 32 MFMA tiles (BM 128:
-// 2 x 2 tiles per wave, one A and one B LDS dword per two MFMAs instead of per one; BM 32 / 64 for the
-// 32- / 64-channel convs, which the 64-row tile ran half / fully padded or on one tile row).  Same
-// K-steps and slices as gemm64_mf_kernel, each output one accumulator fed k in order: bit-identical.
-// LDS rows are BM + 32 (or BM when BM % 64 == 32) floats apart, so the two k rows an MFMA operand read
-// touches (lanes h = 0 / 1) land on disjoint halves of the 64 banks.
-template <class P, bool SPLIT, int BM>
-__global__ __launch_bounds__(256) void gemm128_mf_kernel(P p, int ks, float* slab, int Z) {
-  typedef float f32x16_t __attribute__((ext_vector_type(16)));
-  constexpr int BN = 128, WM = BM >= 64 ? 2 : 1, WN = 4 / WM, TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int SA = BM % 64 ? BM : BM + 32, SB = BN + 32;
-  constexpr int NA = BM >= 64 ? BM / 64 : 1;  // A groups of four per thread
+  constexpr int WM = BM >= 64 ? 2 : 1, WN = 4 / WM, TM = BM / WM / 32, TN = BN / WN / 32;
+  constexpr int PAD = BN == 64 ? 4 : 32, SA = BM % 64 ? BM : BM + PAD, SB = BN + PAD;
+  constexpr int NA = BM >= 64 ? BM / 64 : 1, NB = BN / 64;  // A / B groups of four per thread
   __shared__ __attribute__((aligned(16))) float As[16][SA];
   __shared__ __attribute__((aligned(16))) float Bs[16][SB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / WN, wn = wave % WN;
@@ -165,23 +70,26 @@ __global__ __launch_bounds__(256) void gemm128_mf_kernel(P p, int ks, float* sla
   for (int a = 0; a < TM; ++a)
 #pragma unroll
     for (int b = 0; b < TN; ++b) acc[a][b] = f32x16_t{};
-  float va[NA][4], vb[2][4];
+  float va[NA][4], vb[NB][4];
+  // B staged along kk (runs of taps) for the linears and the strided convs, along the output steps
+  // otherwise
   const bool bk = P::B_KCONTIG || p.kcontig();
-  const bool a_on = BM >= 64 || tid < BM * 4;
+  const bool a_on = tid < BM * 4;  // BM 32: the first 128 threads stage the A rows
+  // (whole runs of four inside the tile take the problem's 4-wide loads: A along kk, B along kk
+  // or along the output steps; the values are those of the per-element accessors)
   auto fetch = [&](int k0) {
 #pragma unroll
     for (int u = 0; u < NA; ++u) {
       const int i = u * 64 + (tid >> 2), kq = (tid & 3) * 4;
-      if (a_on && i0 + i < p.M && k0 + kq + 3 < ke) {
+      if ((BM >= 64 || a_on) && i0 + i < p.M && k0 + kq + 3 < ke) {
         ld4(p.aptr(z, i0 + i, k0 + kq), va[u]);
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          va[u][e] = (a_on && i0 + i < p.M && k0 + kq + e < ke) ? p.a(z, i0 + i, k0 + kq + e) : 0.f;
+          va[u][e] = ((BM >= 64 || a_on) && i0 + i < p.M && k0 + kq + e < ke) ? p.a(z, i0 + i, k0 + kq + e) : 0.f;
       }
     }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
+    auto fetch_b = [&](int u) {
       const int g = tid + 256 * u;
       if (bk) {
         const int j = g >> 2, kq = (g & 3) * 4;
@@ -191,13 +99,21 @@ __global__ __launch_bounds__(256) void gemm128_mf_kernel(P p, int ks, float* sla
             vb[u][e] = (j0 + j < p.N && k0 + kq + e < ke) ? p.b(z, k0 + kq + e, j0 + j) : 0.f;
         }
       } else {
-        const int kk = g >> 5, jb = (g & 31) * 4;
+        const int kk = g / (BN / 4), jb = (g % (BN / 4)) * 4;
         if (!(k0 + kk < ke && j0 + jb + 3 < p.N && p.b4(z, k0 + kk, j0 + jb, vb[u]))) {
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             vb[u][e] = (k0 + kk < ke && j0 + jb + e < p.N) ? p.b(z, k0 + kk, j0 + jb + e) : 0.f;
         }
       }
+    };
+    // (a single group is fetched without a loop around it: the one-trip loop, unrolled only late in the
+    // optimiser, left the 64 x 64 conv tile at 58 VGPRs against 56, a wave of occupancy)
+    if constexpr (NB == 1) {
+      fetch_b(0);
+    } else {
+#pragma unroll
+      for (int u = 0; u < NB; ++u) fetch_b(u);
     }
   };
   fetch(kb);
@@ -207,19 +123,19 @@ __global__ __launch_bounds__(256) void gemm128_mf_kernel(P p, int ks, float* sla
 #pragma unroll
     for (int u = 0; u < NA; ++u) {
       const int i = u * 64 + (tid >> 2), kq = (tid & 3) * 4;
-      if (a_on)
+      if (BM >= 64 || a_on)
 #pragma unroll
         for (int e = 0; e < 4; ++e) As[kq + e][i] = va[u][e];
     }
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+    for (int u = 0; u < NB; ++u) {
       const int g = tid + 256 * u;
       if (bk) {
         const int j = g >> 2, kq = (g & 3) * 4;
 #pragma unroll
         for (int e = 0; e < 4; ++e) Bs[kq + e][j] = vb[u][e];
       } else {
-        const int kk = g >> 5, jb = (g & 31) * 4;
+        const int kk = g / (BN / 4), jb = (g % (BN / 4)) * 4;
         *reinterpret_cast<float4*>(&Bs[kk][jb]) = make_float4(vb[u][0], vb[u][1], vb[u][2], vb[u][3]);
       }
     }
@@ -239,7 +155,9 @@ __global__ __launch_bounds__(256) void gemm128_mf_kernel(P p, int ks, float* sla
     }
     __syncthreads();
   }
-  // per 32 x 32 tile, four rows at a time: their epilogue loads, then their stores (as gemm64_mf_kernel)
+  // per 32 x 32 tile, the epilogue's loads (bias, residual, accumulated-onto values) issued four rows at a
+  // time before their stores (which they could alias as far as the compiler knows): 4 memory round trips
+  // per tile instead of 16 (four rows, not more: registers, the occupancy of the main loop)
 #pragma unroll
   for (int x = 0; x < TM; ++x)
 #pragma unroll
@@ -270,11 +188,6 @@ __global__ __launch_bounds__(256) void gemm128_mf_kernel(P p, int ks, float* sla
     }
 }
 
-// Launches of >= MIMI_WIDE_N columns and >= 192 wide blocks (fewer left CUs idle: a 4096-column decode
-// conv ran 620 us on 128 blocks against 324 on 512 64-tiles), except 1-tap convs, take
-// gemm128_mf_kernel (profiles/r04_ab_mimi_wide.txt)
-constexpr int MIMI_WIDE_N = 256;
-
 // the split-K slices of every output, added in slice order, then the problem's epilogue
 template <class P>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(P p, const float* slab, int ks, int Z) {
@@ -298,23 +211,16 @@ static int mimi_splitk(int KD, int blocks, size_t slab_per_slice) {
   return ks;
 }
 
-template <class P, int BM>
-static void launch_wide(const P& pr, dim3 grid, int ks, float* ws, hipStream_t st) {
-  const int Z = (int)grid.z;
-  const dim3 g((pr.N + 127) / 128, (pr.M + BM - 1) / BM, grid.z);
-  if (ks <= 1 || !ws) {
-    hipLaunchKernelGGL((gemm128_mf_kernel<P, false, BM>), g, dim3(256), 0, st, pr, 1, nullptr, Z);
-    return;
-  }
-  hipLaunchKernelGGL((gemm128_mf_kernel<P, true, BM>), dim3(g.x, g.y, g.z * ks), dim3(256), 0, st, pr, ks, ws, Z);
-  const size_t tot = (size_t)Z * pr.M * pr.N;
-  const int rb = (int)std::min<size_t>(2048, (tot + 255) / 256);
-  hipLaunchKernelGGL(splitk_reduce_kernel<P>, dim3(rb), dim3(256), 0, st, pr, ws, ks, Z);
-}
+// Launches of >= MIMI_WIDE_N columns and >= 192 wide blocks (fewer left CUs idle: a 4096-column decode
+// conv ran 620 us on 128 blocks against 324 on 512 64-tiles), except 1-tap convs, take the BM x 128
+// tiles (profiles/r04_ab_mimi_wide.txt)
+constexpr int MIMI_WIDE_N = 256;
 
 // The host-side choice of every tiled launch, in one place: M x N outputs per grid z (Z of them), KD deep;
 // blocks64 = the 64 x 64 tiles of the batch-folded column space and slab = the outputs of one split-K slice
-// (mimi_splitk's inputs, so a wide launch splits exactly as the 64-tile one would: same sums).
+// (mimi_splitk's inputs).  A wide plan never splits: >= 192 wide blocks of >= 256 columns cover more than 256
+// tiles of 64 x 64, where mimi_splitk no longer doubles.  ks is reported as computed, not clamped: launch_tile
+// refuses a wide split, and tests/test_abi_cpu.py::test_mimi_wide_plan_never_splits sweeps the thresholds.
 static MimiPlan mimi_plan_gemm(int M, int N, int Z, int KD, int blocks64, size_t slab, bool wide_ok, bool have_ws,
                                int fold) {
   MimiPlan pl{MIMI_KERNEL_GEMM64, 0, have_ws ? mimi_splitk(KD, blocks64, slab) : 1, fold};
@@ -327,26 +233,28 @@ static MimiPlan mimi_plan_gemm(int M, int N, int Z, int KD, int blocks64, size_t
   return pl;
 }
 
-// grid: the 64 x 64 tile grid
-template <class P>
-static void launch_gemm64(const P& pr, dim3 grid, const MimiPlan& pl, float* ws, hipStream_t st) {
-  const int ks = pl.ks;
-  if (pl.kernel == MIMI_KERNEL_WIDE) {
-    if (pl.bm == 32) launch_wide<P, 32>(pr, grid, ks, ws, st);
-    else if (pl.bm == 64) launch_wide<P, 64>(pr, grid, ks, ws, st);
-    else launch_wide<P, 128>(pr, grid, ks, ws, st);
-    return;
-  }
+// One tiled launch on BM x BN tiles, Z grid layers of pr.M x pr.N outputs: the kernel with its epilogue, or
+// (ks > 1) its ks K slices into ws and their reduce.  The split is instantiated for the 64 x 64 tile alone.
+template <class P, int BM, int BN>
+static void launch_tile(const P& pr, int Z, int ks, float* ws, hipStream_t st) {
+  if (BN != 64 && ks > 1) throw CsmError(CSM_ERR_HIP, "mimi: a wide-tile plan with split-K (ks " + std::to_string(ks) + ")");
+  const dim3 g((pr.N + BN - 1) / BN, (pr.M + BM - 1) / BM, Z);
   if (ks <= 1 || !ws) {
-    hipLaunchKernelGGL((gemm64_mf_kernel<P, false>), grid, dim3(256), 0, st, pr, 1, nullptr, (int)grid.z);
-    return;
+    hipLaunchKernelGGL((gemm_mf_kernel<P, false, BM, BN>), g, dim3(256), 0, st, pr, 1, nullptr, Z);
+  } else if constexpr (BN == 64) {
+    hipLaunchKernelGGL((gemm_mf_kernel<P, true, BM, BN>), dim3(g.x, g.y, g.z * ks), dim3(256), 0, st, pr, ks, ws, Z);
+    const size_t tot = (size_t)Z * pr.M * pr.N;
+    const int rb = (int)std::min<size_t>(2048, (tot + 255) / 256);
+    hipLaunchKernelGGL(splitk_reduce_kernel<P>, dim3(rb), dim3(256), 0, st, pr, ws, ks, Z);
   }
-  const int Z = (int)grid.z;
-  const dim3 g2(grid.x, grid.y, grid.z * ks);
-  hipLaunchKernelGGL((gemm64_mf_kernel<P, true>), g2, dim3(256), 0, st, pr, ks, ws, Z);
-  const size_t tot = (size_t)Z * pr.M * pr.N;
-  const int rb = (int)std::min<size_t>(2048, (tot + 255) / 256);
-  hipLaunchKernelGGL(splitk_reduce_kernel<P>, dim3(rb), dim3(256), 0, st, pr, ws, ks, Z);
+}
+
+template <class P>
+static void launch_gemm(const P& pr, int Z, const MimiPlan& pl, float* ws, hipStream_t st) {
+  if (pl.kernel != MIMI_KERNEL_WIDE) launch_tile<P, 64, 64>(pr, Z, pl.ks, ws, st);
+  else if (pl.bm == 32) launch_tile<P, 32, 128>(pr, Z, pl.ks, ws, st);
+  else if (pl.bm == 64) launch_tile<P, 64, 128>(pr, Z, pl.ks, ws, st);
+  else launch_tile<P, 128, 128>(pr, Z, pl.ks, ws, st);
 }
 
 // ---------------------------------------------------------------------------- causal conv1d
@@ -447,8 +355,7 @@ MimiPlan mimi_plan_conv1d(const ConvParams& p) {
 void launch_conv1d(const ConvParams& p, hipStream_t st) {
   const MimiPlan pl = mimi_plan_conv1d(p);
   ConvProblem pr{p, p.Cout, pl.fold ? p.B * p.Tout : p.Tout, pl.fold};
-  dim3 grid((pr.N + 63) / 64, (p.Cout + 63) / 64, pl.fold ? 1 : p.B);
-  launch_gemm64(pr, grid, pl, p.ks_ws, st);
+  launch_gemm(pr, pl.fold ? 1 : p.B, pl, p.ks_ws, st);
 }
 
 // ---------------------------------------------------------------------------- transposed conv (k = 2s)
@@ -519,8 +426,7 @@ MimiPlan mimi_plan_convtr(const ConvTrParams& p) {
 void launch_convtr(const ConvTrParams& p, hipStream_t st) {
   const MimiPlan pl = mimi_plan_convtr(p);
   ConvTrProblem pr{p, p.Cout, pl.fold ? p.B * p.n_in : p.n_in, pl.fold};
-  dim3 grid((pr.N + 63) / 64, (p.Cout + 63) / 64, pl.fold ? p.s : p.B * p.s);
-  launch_gemm64(pr, grid, pl, p.ks_ws, st);
+  launch_gemm(pr, pl.fold ? p.s : p.B * p.s, pl, p.ks_ws, st);
 }
 
 // ---------------------------------------------------------------------------- linear (rows x W^T)
@@ -571,7 +477,7 @@ struct LinProblem {
   __device__ void store(int z, int n, int m, float v) const { post(z, n, m, v, pre(z, n, m)); }
 };
 
-// Few rows (streaming decode_step: one row per utterance): gemm64's 64 x 64 tiles leave most of the
+// Few rows (streaming decode_step: one row per utterance): 64 x 64 tiles leave most of the
 // chip idle (8-32 blocks), so row-major linears of <= 32 rows go through the decode GEMV instead
 // (fp32 weights, same epilogues: y = gelu(v) / out += scale * v).  Measured: config 3 (B = 32
 // decode_step) 2083 -> 2123 frames/s; at 125 rows (one-shot decode of a 10 s utterance) neutral, and
@@ -600,8 +506,7 @@ void launch_linear(const LinParams& p, hipStream_t st) {
     return;
   }
   LinProblem pr{p, p.N, p.M};
-  dim3 grid((p.M + 63) / 64, (p.N + 63) / 64, 1);
-  launch_gemm64(pr, grid, pl, p.ks_ws, st);
+  launch_gemm(pr, 1, pl, p.ks_ws, st);
 }
 
 // ============================================================================ LayerNorm rows

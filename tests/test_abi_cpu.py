@@ -209,3 +209,53 @@ def test_q4_gemv_shapes():
     assert L.csm_q4_gemv_shape(1024, 1280, out) == 1 and list(out) == [64, 1, 8]
     assert L.csm_q4_gemv_shape(1023, 1024, out) == 0            # the pair epilogue needs even N
     assert L.csm_q4_gemv_shape(1024, 96, out) == 0              # K a multiple of the group
+
+
+def test_mimi_wide_plan_never_splits():
+    """The codec GEMM plan (mimi_plan_gemm through mimi_lab_plan: host code, no GPU): a launch that takes the
+    BM x 128 tiles never splits K -- >= 192 wide blocks of >= 256 columns cover more than the 256 tiles of
+    64 x 64 at which mimi_splitk stops doubling -- so the split kernel exists for the 64 x 64 tile alone and the
+    launcher refuses a wide split.  The grid brackets every threshold of the plan: output channels around the
+    tile heights (32, 64, 128) and 1024, columns around the wide minimum (256), the next 128-column tiles and
+    several thousand (and the folded short windows), batches 1 .. 128, the four transposed-conv strides,
+    K 16 .. 8192 around the 128 below which nothing splits.  Strides are 0 (the plan reads none; the lab's size
+    checks then admit every combination)."""
+    from csm_mlx import _lib
+    L = _lib.lib()
+    WIDE = 2
+    out = np.zeros(4, np.int32)
+    chans = (31, 32, 33, 63, 64, 65, 66, 127, 128, 129, 130, 1024)
+    cols = (2, 6, 63, 64, 254, 255, 256, 257, 258, 382, 383, 384, 385, 386, 4096, 8200)
+    batches = (1, 2, 3, 4, 8, 16, 32, 47, 48, 64, 96, 127, 128)
+    seen = {}
+
+    def plan(op, geo):
+        g = np.ascontiguousarray(geo, np.int32)
+        _lib.check(L.mimi_lab_plan(op, _lib.ptr(g), len(g), _lib.ptr(out)))
+        kernel, bm, ks, fold = (int(v) for v in out)
+        s = seen.setdefault(op, dict(wide=0, split=0, bm=set()))
+        s["split"] += ks > 1
+        if kernel == WIDE:
+            s["wide"] += 1
+            s["bm"].add(bm)
+            assert ks == 1, (op, list(geo), kernel, bm, ks, fold)
+
+    for Cout in chans:
+        for n in cols:
+            for B in batches:
+                # conv1d, the decoder's window form (stride 1, pad_l 0): K = Cin * k
+                for Cin, k in ((8, 2), (32, 2), (21, 3), (64, 2), (43, 3), (128, 2), (512, 2), (585, 7), (4096, 2)):
+                    plan(0, [Cin, n + k - 1, 0, 0, 0, Cout, k, 1, 1, 0, 0, 0, n, 0, 0, 0, 0, 0, 0, B, 0])
+                # transposed conv: K = 2 Cin, one grid layer per phase
+                for s in (4, 5, 6, 8):
+                    for Cin in (8, 32, 63, 64, 65, 512, 4096):
+                        plan(1, [Cin, n + 1, 0, 0, 0, Cout, s, 0, 1, n, 0, 0, 0, B])
+    # linear: N features are the tile's rows, the M activation rows its columns
+    for N in chans:
+        for M in sorted(set(cols) | {4 * c for c in cols} | {16 * c for c in cols}):
+            for K in (16, 64, 127, 128, 129, 256, 1024, 8192):
+                if M * max(K, N) <= 1 << 28:        # the lab's array-size limit
+                    plan(2, [M, K, K, N, N, 0, 0, 0, 0, 0])
+    for op in (0, 1, 2):
+        assert seen[op]["wide"] > 100 and seen[op]["split"] > 100, (op, seen[op])
+        assert seen[op]["bm"] == {32, 64, 128}, (op, seen[op])

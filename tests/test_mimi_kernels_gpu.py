@@ -545,5 +545,5 @@ def test_table_reaches_every_branch():
         return c["Cin"] * c["k"] if c["op"] == 0 else c["Cin"] * 2 if c["op"] == 1 else c["K"]
     for op in (0, 1, 2):
         assert any(c["op"] == op and p["ks"] > 1 and kdim(c) % 16 for c, p in zip(cases, plans)), op
-    # (no wide launch splits: >= 192 wide blocks are >= 384 64 x 64 tiles, past the 256 at which mimi_splitk still doubles)
+    # (no wide launch splits: tests/test_abi_cpu.py::test_mimi_wide_plan_never_splits sweeps the plan's thresholds)
     assert {c["op"] for c, p in zip(cases, plans) if p["kernel"] == WIDE} == {0, 1, 2}
