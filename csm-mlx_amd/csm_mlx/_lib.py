@@ -90,6 +90,9 @@ def lib():
             "csm_frame_forced": ([P, P, P, P, P], I),
             "csm_frame_host_step": ([P, P, P, ctypes.POINTER(I)], I),
             "csm_read_codes": ([P, P, P, P, ctypes.POINTER(I)], I),
+            "csm_slot_restart": ([P, I, U64], I),
+            "csm_slot_release": ([P, I], I),
+            "csm_slot_read": ([P, I, P, I, ctypes.POINTER(I), ctypes.POINTER(ctypes.c_uint8)], I),
             "csm_debug_read": ([P, ctypes.c_char_p, P, I64, ctypes.POINTER(I64)], I),
             "csm_codes_device_ptr": ([P, ctypes.POINTER(P)], I),
             "csm_read_rows": ([P, ctypes.c_char_p, I, P, P], I),

@@ -1,0 +1,205 @@
+"""Continuous batching: utterances join and leave a running batch.
+
+``generate_batch`` runs B utterances as one indivisible generation: they start together and every frame
+runs all B rows until the slowest ends.  ``SlotBatch`` runs the same frame graphs over B *slots*: a slot
+whose utterance reached EOS (or its frame cap) is read, then restarted with the next queued prompt at the
+next frame boundary -- or parked when the queue is empty -- while the other slots go on
+(csm_slot_restart / csm_slot_release / csm_slot_read, csrc/csm_engine_slots.hip).  The codes of an
+utterance depend only on its prompt, its seed, the sampler and the processors: not on the slot, on when it
+joined, on who ran beside it or on what ran in the slot before.
+
+No reference counterpart: the reference speaks one sentence per ``stream_generate`` call
+(run_streaming_csm_mlx.py ``tts_worker``); this is what a server with several such conversations on one
+GPU puts between them and the engine.
+"""
+from __future__ import annotations
+
+import collections
+import ctypes
+from typing import Callable, Generator, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+from .generation import (FrameCache, _check_window, _decode_batch, _resolve_sampler, _seed_list,
+                         device_processors)
+from .models import CSM
+from .sampling import HostSampler, Sampler
+
+DEFAULT_CHUNK = 8
+
+
+class _EngineSlots:
+    """The engine's side of a ``SlotBatch``: one ``FrameCache`` (csm_begin, the sampler filters, the c0
+    processors, the superseded check) plus the three slot calls.  ``SlotBatch`` only talks to these
+    methods, so its scheduling is testable against a stub with the same ones."""
+
+    def __init__(self, model: CSM, slots: int, sampler: Sampler, processors):
+        self.model = model
+        self.cache = FrameCache(model, slots, sampler, np.zeros(slots, np.uint64), processors)
+        self.L = self.cache.L
+
+    def restart(self, b: int, seed: int):
+        self.cache._check()
+        _lib.check(self.L.csm_slot_restart(self.model.engine, b, ctypes.c_uint64(int(seed) & ((1 << 64) - 1))))
+
+    def release(self, b: int):
+        self.cache._check()
+        _lib.check(self.L.csm_slot_release(self.model.engine, b))
+
+    def prefill(self, items: Sequence[Tuple[int, np.ndarray, np.ndarray]]):
+        self.cache.prefill_batch(items)
+
+    def run(self, nframes: int):
+        """nframes frames for every slot, waited for (the wait also checks the persistent kernels'
+        hand-off error flags: all three)."""
+        self.cache.run(nframes, sync=True)
+
+    def poll(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(n_frames [B], done [B]) of the slots' current utterances."""
+        self.cache._check()
+        n = np.zeros(self.cache.B, np.int32)
+        d = np.zeros(self.cache.B, np.uint8)
+        _lib.check(self.L.csm_read_codes(self.model.engine, None, _lib.ptr(n), _lib.ptr(d), None))
+        return n, d.astype(bool)
+
+    def read(self, b: int, cap: int) -> np.ndarray:
+        """codes (F, K) int32 of slot b's utterance (EOS excluded)."""
+        self.cache._check()
+        out = np.zeros((max(cap, 1), self.model.n_audio_codebooks), np.int32)
+        n = ctypes.c_int(0)
+        d = ctypes.c_uint8(0)
+        _lib.check(self.L.csm_slot_read(self.model.engine, b, _lib.ptr(out), cap, ctypes.byref(n), ctypes.byref(d)))
+        return out[: n.value].copy()
+
+
+class _Job:
+    __slots__ = ("ticket", "tokens", "mask", "cap", "seed", "ran")
+
+    def __init__(self, ticket, tokens, mask, cap, seed):
+        self.ticket, self.tokens, self.mask, self.cap, self.seed, self.ran = ticket, tokens, mask, cap, seed, 0
+
+
+class SlotBatch:
+    """A batch of ``slots`` slots over ``model``'s engine, each holding at most one utterance.
+
+    ``submit`` queues a prompt; ``run`` is a generator that yields ``(ticket, codes (F, K) int32)`` as
+    utterances finish and ends when the queue and the slots are empty (more can be submitted while it
+    runs: they join at the next frame boundary).  Every chunk runs ``min(chunk, smallest remaining frame
+    budget among the active slots)`` frames, then waits and polls, so no slot ever runs past its own cap
+    and the reference's window guard (prompt rows < max_seq_len - max_audio_frames) stays the only
+    admission rule; a slot runs at most ``chunk - 1`` frames past its EOS, which are discarded.
+
+    The sampler runs on the GPU, and so must the processors (``device_processors``): a ``HostSampler`` or
+    any other processor list pauses every frame for the host and has nothing to batch -- ``ValueError``.
+    Creating a SlotBatch supersedes older ``FrameCache``s (and SlotBatches) of the model exactly as a new
+    ``FrameCache`` does."""
+
+    def __init__(self, model, slots: int, *, sampler, logits_processors: Optional[List[Callable]] = None,
+                 chunk: int = DEFAULT_CHUNK, _engine=None):
+        if slots < 1:
+            raise ValueError("a SlotBatch needs at least one slot")
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        if isinstance(sampler, HostSampler) or not isinstance(sampler, Sampler):
+            raise ValueError("SlotBatch samples on the GPU: pass a csm_mlx.sampling.Sampler (a host sampler "
+                             "callable pauses every frame for the host and has nothing to batch)")
+        on_device = device_processors(logits_processors, sampler)
+        if logits_processors and on_device is None:
+            raise ValueError("SlotBatch runs logits processors on the GPU only: at most one logit_bias followed "
+                             "by at most one repetition_penalty (make_logits_processors); other lists pause "
+                             "every frame for the host")
+        self.model = model
+        self.slots = slots
+        self.chunk = chunk
+        self.max_frames = int(getattr(model, "max_frames", 0) or model.max_seq_len)
+        self._eng = _engine if _engine is not None else _EngineSlots(model, slots, sampler, on_device)
+        self._queue: collections.deque = collections.deque()
+        self._active: List[Optional[_Job]] = [None] * slots
+        self._parked = [False] * slots
+        self._tickets = 0
+
+    def submit(self, tokens, mask, max_audio_frames: int, seed: int = 0) -> int:
+        """Queue one utterance: prompt (L, K+1) tokens / mask, at most ``max_audio_frames`` frames, its
+        sampling seed.  Returns the ticket ``run`` yields its codes under."""
+        tokens = np.ascontiguousarray(tokens, np.int32)
+        mask = np.ascontiguousarray(np.asarray(mask).astype(bool), np.uint8)
+        cap = int(max_audio_frames)
+        if cap < 0:
+            raise ValueError("max_audio_frames must be >= 0")
+        _check_window(self.model, tokens.shape[0], cap)                          # generation.py:131-137
+        if cap > self.max_frames:     # the engine would refuse the frames that take it there (CSM_ERR_STATE)
+            raise _lib.CsmHipError(_lib.CSM_ERR_STATE, f"an utterance of up to {cap} frames does not fit the engine's "
+                                   f"{self.max_frames}-frame code history (CSM(..., max_frames=))")
+        ticket = self._tickets
+        self._tickets += 1
+        self._queue.append(_Job(ticket, tokens, mask, cap, seed))
+        return ticket
+
+    def _fill(self) -> Generator[Tuple[int, np.ndarray], None, None]:
+        """A frame boundary: free slots take the next queued prompts (all of the boundary's joins in one
+        batched prefill); slots left without work are parked."""
+        K = self.model.n_audio_codebooks
+        joins = []
+        for b in range(self.slots):
+            if self._active[b] is not None:
+                continue
+            while self._queue and self._queue[0].cap == 0:      # nothing to generate: an empty result
+                yield self._queue.popleft().ticket, np.zeros((0, K), np.int32)
+            if self._queue:
+                job = self._queue.popleft()
+                self._eng.restart(b, job.seed)
+                self._active[b] = job
+                self._parked[b] = False
+                joins.append((b, job.tokens, job.mask))
+            elif not self._parked[b]:
+                self._eng.release(b)
+                self._parked[b] = True
+        if joins:
+            self._eng.prefill(joins)
+
+    def run(self) -> Generator[Tuple[int, np.ndarray], None, None]:
+        while True:
+            yield from self._fill()
+            active = [j for j in self._active if j is not None]
+            if not active:             # (with every slot free, _fill has emptied the queue)
+                return
+            n = min(self.chunk, min(j.cap - j.ran for j in active))
+            self._eng.run(n)
+            _, done = self._eng.poll()
+            for b, job in enumerate(self._active):
+                if job is None:
+                    continue
+                job.ran += n
+                if done[b] or job.ran >= job.cap:
+                    codes = self._eng.read(b, job.cap)
+                    self._active[b] = None
+                    yield job.ticket, codes
+
+
+def generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], max_audio_length_ms: float = 10_000,
+                   *, slots: int, temperature: float = 0.0, top_k: int = 0, sampler=None, seeds=None,
+                   max_audio_frames: Optional[Sequence[int]] = None, decode: bool = True, with_codes: bool = False,
+                   logits_processors: Optional[List[Callable]] = None, chunk: int = DEFAULT_CHUNK):
+    """``generate_batch`` for any number of prompts through ``slots`` slots: list of waveforms in prompt
+    order (or codes if decode=False; (codes, waveforms) with ``with_codes``).  ``max_audio_frames``: one
+    frame cap per prompt (default: ``max_audio_length_ms`` for all).  Seeds follow ``generate_batch``: a
+    scalar s gives s + i for prompt i."""
+    smp = _resolve_sampler(temperature, sampler, top_k)
+    n = len(prompts)
+    caps = [int(max_audio_length_ms / 80)] * n if max_audio_frames is None else [int(c) for c in max_audio_frames]
+    if len(caps) != n:
+        raise ValueError("need one frame cap per prompt")
+    seed_list = _seed_list(seeds, n)
+    batch = SlotBatch(model, slots, sampler=smp, logits_processors=logits_processors, chunk=chunk)
+    tickets = [batch.submit(t, m, caps[i], int(seed_list[i])) for i, (t, m) in enumerate(prompts)]
+    got = dict(batch.run())
+    codes = [got[t] for t in tickets]
+    if not decode:
+        return codes
+    n_frames = np.array([len(c) for c in codes], np.int32)
+    hist = np.zeros((int(n_frames.max()) if n else 0, n, model.n_audio_codebooks), np.int32)
+    for i, c in enumerate(codes):
+        hist[: len(c), i] = c
+    pcm = _decode_batch(model, hist, n_frames)
+    return (codes, pcm) if with_codes else pcm

@@ -62,9 +62,12 @@ def default_device() -> int:
 
 class CSM:
     """models.py:31-92.  ``dtype`` selects weight storage: "bf16" (perf), "float32" (parity) or "q4"
-    (int4 g64, as after ``nn.quantize(model, 64, 4)``; see ``quantize``)."""
+    (int4 g64, as after ``nn.quantize(model, 64, 4)``; see ``quantize``).  ``max_frames``: the capacity of
+    the engine's code history in frames (default ``max_seq_len``): the most frames one batch -- in a
+    ``SlotBatch``, one utterance -- can generate."""
 
-    def __init__(self, args: ModelArgs, *, dtype: str = "bf16", device: Optional[int] = None, max_batch: int = 1):
+    def __init__(self, args: ModelArgs, *, dtype: str = "bf16", device: Optional[int] = None, max_batch: int = 1,
+                 max_frames: Optional[int] = None):
         self.args = args
         self.n_text_vocab = args.n_text_vocab
         self.n_audio_vocab = args.n_audio_vocab
@@ -82,6 +85,9 @@ class CSM:
         self.device = default_device() if device is None else device
         self.max_seq_len = bb.max_position_embeddings or 2048      # generation.py:132
         self._max_batch = max_batch
+        if max_frames is not None and max_frames < 1:
+            raise ValueError("max_frames must be >= 1")
+        self.max_frames = self.max_seq_len if max_frames is None else int(max_frames)
         self._engine = None
         self._loaded = set()
         self._sources = []     # checkpoint paths / dicts given to load_weights (load_adapters re-reads them)
@@ -98,7 +104,7 @@ class CSM:
             h = ctypes.c_void_p()
             wdt = {"float32": _lib.CSM_F32, "bf16": _lib.CSM_BF16, "q4": _lib.CSM_Q4}[self.dtype]
             _lib.check(L.csm_engine_create(ctypes.byref(self._dims()), self.device, wdt, self._max_batch,
-                                           self.max_seq_len, ctypes.byref(h)))
+                                           self.max_frames, ctypes.byref(h)))
             self._engine = h
             for which, st in ((0, self.backbone.args), (1, self.decoder.args)):
                 t = llama3_rope_table(st, self.max_seq_len)

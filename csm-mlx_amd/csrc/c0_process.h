@@ -33,3 +33,8 @@ __device__ __forceinline__ int c0_window_n(int f, int context, float penalty) {
 __device__ __forceinline__ int c0_window_code(const int* hist, int f, int j, int b, int B, int K) {
   return hist[((size_t)(f - 1 - j) * B + b) * K];
 }
+// The same entry when the history is a ring of F_cap rows over the global frame index f (j < the utterance's
+// own frame count <= f, so f - 1 - j >= 0; the identity of c0_window_code while f <= F_cap)
+__device__ __forceinline__ int c0_window_code_ring(const int* hist, int f, int j, int b, int B, int K, int F_cap) {
+  return hist[((size_t)((f - 1 - j) % F_cap) * B + b) * K];
+}

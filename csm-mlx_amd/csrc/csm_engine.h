@@ -2,6 +2,7 @@
 //   csm_engine.hip          frame paths: the block stacks, path selection, body / head enqueue, graph capture
 //   csm_engine_weights.hip  lifecycle and weights: create / destroy, loader, quantizer, derived tables
 //   csm_engine_abi.hip      frame ABI: csm_begin, prefill, csm_run_frames*, csm_frame_*, csm_read_codes
+//   csm_engine_slots.hip    continuous batching: csm_slot_restart / csm_slot_release / csm_slot_read
 //   csm_engine_lab.hip      lab and inspection: csm_bench_*, debug taps, csm_linear, csm_set_option
 #pragma once
 #include <hip/hip_runtime.h>
@@ -173,6 +174,17 @@ struct csm_engine {
   int frames_run = 0;
   bool need_body = false;
   std::vector<int> prompt_len;
+  // Continuous batching (csm_engine_slots.hip): the B rows are slots whose utterances start (csm_slot_restart)
+  // and leave (csm_slot_release) at frame boundaries while the others go on.  slot_frame[b] is the utterance's
+  // own frame index -- what the samplers' counters, the EOS test, n_frames and the c0 repetition window count
+  // in; after a plain csm_begin it equals frame_ctr[0] for every row.  parked[b] marks a slot with no
+  // utterance: its position stays 0 and its done flag set.  The code history is then a ring over the global
+  // frame index and slot_first[b] is the global frame at which slot b's utterance started.
+  int* slot_frame = nullptr;  // [B_max]
+  uint8_t* parked = nullptr;  // [B_max]
+  bool slot_mode = false;     // from the first slot call after csm_begin until the next csm_begin
+  std::vector<char> parked_host;
+  std::vector<int> slot_first;
   // graphs
   hipGraphExec_t g_body = nullptr, g_head = nullptr;
   int g_B = -1;
@@ -314,5 +326,7 @@ void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piec
 void enqueue_head(csm_engine* e, hipStream_t st);
 hipGraphExec_t capture(csm_engine* e, void (*fn)(csm_engine*, hipStream_t));
 void check_handoffs(csm_engine* e);
+// csm_engine_abi.hip
+void body_if_needed(csm_engine* e, bool graph = false);
 
 #pragma GCC visibility pop

@@ -184,7 +184,7 @@ bool has_down_copies(csm_engine* e, const Stack& s) {
 AdvanceParams advance_params(csm_engine* e) {
   AdvanceParams ap{};
   ap.codes = e->codes; ap.hist = e->hist; ap.F_cap = e->F_cap; ap.B = e->B; ap.K = e->K; ap.V = e->V; ap.done = e->done;
-  ap.n_frames = e->n_frames; ap.frame_ctr = e->frame_ctr;
+  ap.n_frames = e->n_frames; ap.frame_ctr = e->frame_ctr; ap.slot_frame = e->slot_frame;
   return ap;
 }
 
@@ -220,7 +220,7 @@ void enqueue_body(csm_engine* e, hipStream_t st) {
   const int B = e->B;
   EmbedParams ep{};
   ep.codes = e->codes; ep.text_emb = e->text_emb; ep.audio_emb = e->audio_emb; ep.V = e->V; ep.K = e->K;
-  ep.D = e->D; ep.out = e->x; ep.pos_inc = e->pos;
+  ep.D = e->D; ep.out = e->x; ep.pos_inc = e->pos; ep.parked = e->parked;
   // batched backbone rows on the streaming GEMM (round 4 default; option bb_xs / CSM_BB_XS=0: gemm_wide)
   const bool bb_xs = e->bb_xs_on && !bb_step_eligible(e) && bb_xs_eligible(e, B);
   if (bb_xs) {
@@ -244,6 +244,7 @@ void enqueue_body(csm_engine* e, hipStream_t st) {
 // one workgroup per CU assumes.
 bool dec_frame_eligible(csm_engine* e) {
   Handoff& h = e->h_df;
+  if (e->slot_mode) return false;  // its sampler counter and c0 window read the global frame index
   if (!h.on || e->B != 1 || (e->wdt != WDT_BF16 && e->wdt != WDT_Q4) || e->head_wdt != WDT_BF16) return false;
   if (e->temperature > 0.f && (e->use_top_p || e->use_min_p)) return false;  // filters: sample_filtered_kernel
   if (!csm1b_decoder(e->dec.d) || e->dec.d.n_layers != DEC_FRAME_LAYERS || e->bb.d.hidden != 2048 || e->V <= 2048 ||
@@ -320,7 +321,7 @@ void launch_xsd(csm_engine* e, int M, int i, const unsigned long long* part_prev
     a.head_out = e->ci_logits + (size_t)(i - 1) * e->B * Vp; a.head_part = part_out;
     if (sample) {
       a.sample = 1; a.s_top_k = e->top_k; a.s_K = e->K; a.s_cb = i; a.s_temperature = e->temperature;
-      a.s_seeds = e->seeds; a.s_frame_ctr = e->frame_ctr;
+      a.s_seeds = e->seeds; a.s_slot_frame = e->slot_frame;
     }
   }
   launch_dec_step_xs(a, st, e->wdt == WDT_Q4);
@@ -422,7 +423,7 @@ void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piec
   auto part = [&](int cb) { return e->part + (size_t)cb * e->B_max * e->part_stride; };
   SampleParams sp{};
   sp.ls = Vp; sp.V = V; sp.temperature = e->temperature; sp.top_k = e->top_k; sp.seeds = e->seeds;
-  sp.frame_ctr = e->frame_ctr; sp.K = K; sp.codes = e->codes; sp.part_stride = e->part_stride;
+  sp.slot_frame = e->slot_frame; sp.K = K; sp.codes = e->codes; sp.part_stride = e->part_stride;
   sp.use_top_p = e->use_top_p; sp.use_min_p = e->use_min_p; sp.min_keep = e->min_keep;
   sp.top_p_cut = e->top_p_cut; sp.log_min_p = e->log_min_p;
   sp.forced = host_codes ? e->force : nullptr;
@@ -436,7 +437,8 @@ void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piec
   if (c0_proc) {
     C0ProcessParams cp{};
     cp.logits = e->c0_logits; cp.ls = Vp; cp.V = V; cp.bias = e->c0_bias_on ? e->c0_bias : nullptr; cp.penalty = e->c0_penalty;
-    cp.context = e->c0_context; cp.hist = e->hist; cp.B = B; cp.K = K; cp.frame_ctr = e->frame_ctr;
+    cp.context = e->c0_context; cp.hist = e->hist; cp.B = B; cp.K = K; cp.F_cap = e->F_cap;
+    cp.frame_ctr = e->frame_ctr; cp.slot_frame = e->slot_frame;
     launch_c0_process(cp, st);
   }
   const bool pieces = phase == HeadPhase::HostPiece;

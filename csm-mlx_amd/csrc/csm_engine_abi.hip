@@ -4,23 +4,24 @@
 namespace {
 
 // The checks every call that starts a frame makes (each caller keeps its own order among its other checks)
-void require_prefilled(csm_engine* e) {
+void require_prefilled(csm_engine* e) {  // (a parked slot has no prompt and needs none)
   for (int b = 0; b < e->B; ++b)
-    if (e->prompt_len[b] < 0) throw CsmError(CSM_ERR_STATE, "csm_prefill not called for every utterance");
+    if (e->prompt_len[b] < 0 && !e->parked_host[b]) throw CsmError(CSM_ERR_STATE, "csm_prefill not called for every utterance");
 }
 void require_window(csm_engine* e, int nframes) {
   int maxpos = 0;
-  for (int b = 0; b < e->B; ++b) maxpos = std::max(maxpos, e->pos_host[b]);
+  for (int b = 0; b < e->B; ++b)
+    if (!e->parked_host[b]) maxpos = std::max(maxpos, e->pos_host[b]);
   if (maxpos + nframes + (e->need_body ? 1 : 0) > e->dims.max_seq_len)
     throw CsmError(CSM_ERR_TOO_LONG, "frames exceed the 2048-position window");
 }
 
-// The backbone row of the previous frame's codes, when one is due: the captured graph or eager launches
-void body_if_needed(csm_engine* e, bool graph = false) {
-  if (!e->need_body) return;
-  if (graph) HIPCHK(hipGraphLaunch(e->g_body, e->st));
-  else enqueue_body(e, e->st);
-  for (int b = 0; b < e->B; ++b) e->pos_host[b] += 1;
+// Slot mode: no utterance may run past the F_cap frames of history that csm_slot_read can still reach
+void require_ring(csm_engine* e, int nframes) {
+  for (int b = 0; b < e->B; ++b)
+    if (!e->parked_host[b] && e->frames_run + nframes - e->slot_first[b] > e->F_cap)
+      throw CsmError(CSM_ERR_STATE, "slot " + std::to_string(b) + ": an utterance longer than the " + std::to_string(e->F_cap) +
+                                        "-frame history (csm_engine_create's max_frames)");
 }
 
 // Waits for the stream; 1 when every utterance of the batch has reached EOS
@@ -34,6 +35,16 @@ int wait_all_done(csm_engine* e) {
 }
 
 }  // namespace
+
+// The backbone row of the previous frame's codes, when one is due: the captured graph or eager launches
+// (a parked slot's position stays where the device keeps it: 0)
+void body_if_needed(csm_engine* e, bool graph) {
+  if (!e->need_body) return;
+  if (graph) HIPCHK(hipGraphLaunch(e->g_body, e->st));
+  else enqueue_body(e, e->st);
+  for (int b = 0; b < e->B; ++b)
+    if (!e->parked_host[b]) e->pos_host[b] += 1;
+}
 
 extern "C" {
 
@@ -64,11 +75,16 @@ int csm_begin(csm_engine* e, int B, const uint64_t* seeds, float temperature, in
     e->frames_run = 0;
     e->need_body = false;
     e->prompt_len.assign(B, -1);
+    e->slot_mode = false;
+    e->parked_host.assign(B, 0);
+    e->slot_first.assign(B, 0);
     std::vector<uint64_t> s(B, 0);
     if (seeds) memcpy(s.data(), seeds, B * 8);
     HIPCHK(hipMemcpyAsync(e->seeds, s.data(), B * 8, hipMemcpyHostToDevice, e->st));
     HIPCHK(hipMemsetAsync(e->done, 0, B, e->st));
     HIPCHK(hipMemsetAsync(e->n_frames, 0, B * 4, e->st));
+    HIPCHK(hipMemsetAsync(e->slot_frame, 0, B * 4, e->st));
+    HIPCHK(hipMemsetAsync(e->parked, 0, B, e->st));
     HIPCHK(hipMemsetAsync(e->frame_ctr, 0, 16, e->st));
     HIPCHK(hipMemsetAsync(e->codes, 0, (size_t)B * e->K * 4, e->st));
     HIPCHK(hipStreamSynchronize(e->st));
@@ -242,7 +258,10 @@ int csm_run_frames(csm_engine* e, int nframes, int* all_done) {
     if (e->c0_pending) throw CsmError(CSM_ERR_STATE, "csm_frame_finish pending");
     require_prefilled(e);
     HIPCHK(hipSetDevice(e->dev));
-    if (e->frames_run + nframes > e->F_cap) nframes = e->F_cap - e->frames_run;
+    // the history is [F_cap] frames: a plain batch stops there; in slot mode it is a ring and only each
+    // utterance's own length is bounded by it
+    if (e->slot_mode) require_ring(e, nframes);
+    else if (e->frames_run + nframes > e->F_cap) nframes = e->F_cap - e->frames_run;
     require_window(e, nframes);
     if (nframes <= 0) { if (all_done) *all_done = 0; return CSM_OK; }
     // CSM_GRAPH=0: eager launches of the same kernels (rocprofv3 kernel tracing of graph
@@ -328,7 +347,7 @@ int csm_run_frames_ahead(csm_engine* e, int nframes, int* prev_all_done) {
 
 int csm_frame_step(csm_engine* e, int32_t* out_codes, uint8_t* done) {
   if (!e) { csm_set_error("null engine"); return CSM_ERR_ARG; }
-  if (e->frames_run >= e->F_cap) { csm_set_error("frame capacity reached"); return CSM_ERR_STATE; }
+  if (!e->slot_mode && e->frames_run >= e->F_cap) { csm_set_error("frame capacity reached"); return CSM_ERR_STATE; }
   const int rc = csm_run_frames(e, 1, nullptr);
   if (rc != CSM_OK) return rc;
   CSM_TRY {
@@ -346,6 +365,7 @@ int csm_frame_step(csm_engine* e, int32_t* out_codes, uint8_t* done) {
 int csm_frame_c0_logits(csm_engine* e, float* logits) {
   CSM_TRY {
     require_prefilled(e);
+    if (e->slot_mode) throw CsmError(CSM_ERR_STATE, "host-paused frames are not available in slot mode");
     if (e->c0_pending) throw CsmError(CSM_ERR_STATE, "csm_frame_c0_logits called again before csm_frame_finish");
     if (!logits) throw CsmError(CSM_ERR_ARG, "null logits buffer");
     HIPCHK(hipSetDevice(e->dev));
@@ -421,6 +441,7 @@ int csm_frame_host_step(csm_engine* e, const int32_t* codes, float* logits, int*
 int csm_frame_forced(csm_engine* e, const int32_t* codes, float* c0_logits, float* ci_logits, float* ce) {
   CSM_TRY {
     require_prefilled(e);
+    if (e->slot_mode) throw CsmError(CSM_ERR_STATE, "teacher-forced frames are not available in slot mode");
     if (e->c0_pending) throw CsmError(CSM_ERR_STATE, "csm_frame_finish pending");
     if (!codes) throw CsmError(CSM_ERR_ARG, "null codes");
     HIPCHK(hipSetDevice(e->dev));
@@ -453,6 +474,8 @@ int csm_read_codes(csm_engine* e, int32_t* hist, int32_t* n_frames, uint8_t* don
     HIPCHK(hipSetDevice(e->dev));
     HIPCHK(hipStreamSynchronize(e->st));
     check_handoffs(e);
+    if (hist && e->slot_mode)
+      throw CsmError(CSM_ERR_STATE, "the history is a ring in slot mode: read a slot's codes with csm_slot_read");
     if (hist)
       HIPCHK(hipMemcpy(hist, e->hist, (size_t)e->frames_run * e->B * e->K * 4, hipMemcpyDeviceToHost));
     if (n_frames) HIPCHK(hipMemcpy(n_frames, e->n_frames, e->B * 4, hipMemcpyDeviceToHost));

@@ -1,0 +1,131 @@
+// CSM engine, continuous batching: the B rows of a batch as slots whose utterances start and leave at frame
+// boundaries while the others go on (csm_slot_restart / csm_slot_release / csm_slot_read).
+//
+// Everything a slot owns sits behind pointers the captured frame graphs already hold -- its position, done
+// flag, frame count, own frame index (the samplers' counter), seed, feedback codes and parked mark -- so a
+// restart rewrites that state with one small kernel on the engine stream and no graph is captured again.
+// The code history stays [F_cap][B][K] but is written as a ring over the global frame index; slot b's
+// utterance occupies the rows from slot_first[b] on.
+#include "csm_engine.h"
+
+namespace {
+
+struct SlotResetParams {
+  uint8_t* done;
+  int* n_frames;
+  int* slot_frame;
+  int* codes;  // [B][K]
+  uint8_t* parked;
+  int* pos;
+  uint64_t* seeds;
+  float* h_last;  // [B][D]
+  int b, K, D;
+  uint64_t seed;
+  int park;  // 1: the slot holds no utterance from here on
+};
+
+// Slot b starts afresh (park 0) or is parked (park 1).  A parked slot's rows still run in every launch: its
+// position stays 0 (embed skips the increment), its done flag is set so the EOS poll never waits for it, and its
+// backbone output is zeroed so its first frame's head reads finite rows whatever ran in the slot before.
+__global__ __launch_bounds__(256) void slot_reset_kernel(SlotResetParams p) {
+  const int t = threadIdx.x, b = p.b;
+  if (t == 0) {
+    p.done[b] = p.park ? 1 : 0;
+    p.n_frames[b] = 0;
+    p.slot_frame[b] = 0;
+    p.parked[b] = p.park ? 1 : 0;
+    p.pos[b] = 0;
+    p.seeds[b] = p.seed;
+  }
+  for (int k = t; k < p.K; k += 256) p.codes[(size_t)b * p.K + k] = 0;
+  if (p.park)
+    for (int d = t; d < p.D; d += 256) p.h_last[(size_t)b * p.D + d] = 0.f;
+}
+
+// The checks and bookkeeping csm_slot_restart and csm_slot_release share
+void slot_reset(csm_engine* e, int b, uint64_t seed, bool park) {
+  if (!e) throw CsmError(CSM_ERR_ARG, "null engine");
+  if (e->B <= 0) throw CsmError(CSM_ERR_STATE, "csm_begin not called");
+  if (b < 0) throw CsmError(CSM_ERR_ARG, "slot index out of range");
+  if (b >= e->B) throw CsmError(CSM_ERR_STATE, "slot " + std::to_string(b) + " beyond the batch of " + std::to_string(e->B));
+  if (e->c0_pending) throw CsmError(CSM_ERR_STATE, "csm_frame_finish pending");
+  HIPCHK(hipSetDevice(e->dev));
+  if (e->ahead_pending) {  // a chunk enqueued by csm_run_frames_ahead: its pinned copies land first
+    HIPCHK(hipStreamSynchronize(e->st));
+    e->ahead_pending = false;
+  }
+  if (!e->slot_mode) {
+    e->slot_mode = true;
+    ++e->filters_id;  // the batch-1 frame decoder leaves the frame graph: capture again
+  }
+  const bool body = !park && e->need_body;
+  if (body)
+    for (int u = 0; u < e->B; ++u)
+      if (!e->parked_host[u] && u != b && e->pos_host[u] + 1 >= e->dims.max_seq_len)
+        throw CsmError(CSM_ERR_TOO_LONG, "rows exceed the 2048-position window");
+  SlotResetParams p{};
+  p.done = e->done; p.n_frames = e->n_frames; p.slot_frame = e->slot_frame; p.codes = e->codes; p.parked = e->parked;
+  p.pos = e->pos; p.seeds = e->seeds; p.h_last = e->h_last; p.b = b; p.K = e->K; p.D = e->D; p.seed = seed; p.park = park ? 1 : 0;
+  hipLaunchKernelGGL(slot_reset_kernel, dim3(1), dim3(256), 0, e->st, p);
+  HIPCHK(hipGetLastError());
+  if (body) {
+    // the other slots' previous frame reaches their KV before this slot's prompt rows are prefilled (prefill
+    // clears need_body): the pending backbone row of the whole batch, eagerly.  It follows the reset, so the
+    // leaving utterance's row lands at position 1 of its slot, inside the cache wherever that utterance
+    // stopped; the prompt the caller prefills next overwrites it and sets the position.
+    body_if_needed(e);
+    e->need_body = false;
+  }
+  e->parked_host[b] = park ? 1 : 0;
+  e->pos_host[b] = park ? 0 : -1;  // a restarted slot's prompt rows start at position 0
+  e->prompt_len[b] = -1;
+  e->slot_first[b] = e->frames_run;
+}
+
+}  // namespace
+
+extern "C" {
+
+int csm_slot_restart(csm_engine* e, int b, uint64_t seed) {
+  CSM_TRY { slot_reset(e, b, seed, false); }
+  CSM_CATCH
+}
+
+int csm_slot_release(csm_engine* e, int b) {
+  CSM_TRY { slot_reset(e, b, 0, true); }
+  CSM_CATCH
+}
+
+int csm_slot_read(csm_engine* e, int b, int32_t* codes, int cap_frames, int* n_frames, uint8_t* done) {
+  CSM_TRY {
+    if (!e) throw CsmError(CSM_ERR_ARG, "null engine");
+    if (b < 0) throw CsmError(CSM_ERR_ARG, "slot index out of range");
+    if (b >= e->B) throw CsmError(CSM_ERR_STATE, "slot " + std::to_string(b) + " beyond the batch of " + std::to_string(e->B));
+    if (codes && cap_frames < 0) throw CsmError(CSM_ERR_ARG, "negative frame capacity");
+    HIPCHK(hipSetDevice(e->dev));
+    HIPCHK(hipStreamSynchronize(e->st));
+    check_handoffs(e);
+    int n = 0;
+    uint8_t d = 0;
+    HIPCHK(hipMemcpy(&n, e->n_frames + b, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&d, e->done + b, 1, hipMemcpyDeviceToHost));
+    if (codes) {
+      const int first = e->slot_first[b];
+      if (n < 0 || n > e->frames_run - first || e->frames_run - first > e->F_cap)
+        throw CsmError(CSM_ERR_STATE, "slot " + std::to_string(b) + ": its frames are no longer in the history");
+      if (n > cap_frames) throw CsmError(CSM_ERR_ARG, "csm_slot_read: " + std::to_string(n) + " frames do not fit the buffer");
+      const size_t K = e->K, pitch = (size_t)e->B * K * 4;
+      for (int i = 0; i < n;) {  // at most two runs of consecutive ring rows
+        const int row = (first + i) % e->F_cap, run = std::min(n - i, e->F_cap - row);
+        HIPCHK(hipMemcpy2D(codes + (size_t)i * K, K * 4, e->hist + ((size_t)row * e->B + b) * K, pitch, K * 4, run,
+                           hipMemcpyDeviceToHost));
+        i += run;
+      }
+    }
+    if (n_frames) *n_frames = n;
+    if (done) *done = d;
+  }
+  CSM_CATCH
+}
+
+}  // extern "C"

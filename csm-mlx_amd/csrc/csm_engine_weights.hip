@@ -63,6 +63,8 @@ void ensure_batch(csm_engine* e, int B) {
   e->hist = (int*)e->balloc((size_t)e->F_cap * Bm * K * 4);
   e->pos = (int*)e->balloc(Bm * 4);
   e->n_frames = (int*)e->balloc(Bm * 4);
+  e->slot_frame = (int*)e->balloc(Bm * 4);
+  e->parked = (uint8_t*)e->balloc(Bm);
   e->done = (uint8_t*)e->balloc(Bm);
   e->seeds = (uint64_t*)e->balloc(Bm * 8);
   // partial slots per row: enough for any head tiling (c0 / ci heads, dense or q4; >= Vp/2 blocks never occur)

@@ -211,6 +211,7 @@ struct EmbedParams {
   float* ss_out;
   int ss_stride;
   float* hs_out;         // int4 consumer: half-group sums of the split rows (xs.h)
+  const uint8_t* parked; // decode mode, optional [M]: a parked slot's position is not advanced (it stays 0)
 };
 
 struct AttnParams {
@@ -251,7 +252,7 @@ struct SampleParams {
   float temperature;
   int top_k;
   const uint64_t* seeds;
-  const int* frame_ctr;
+  const int* slot_frame;  // [B] each utterance's own frame index (the sampler's counter)
   int K, cb;
   int* codes;           // [B][K]
   unsigned long long* part;  // optional: publish the code as partial [b * part_stride]
@@ -266,7 +267,8 @@ struct SampleParams {
 
 // mlx_lm make_logits_processors on the c0 logits, run inside the frame (csm_set_c0_processors; c0_process.h
 // holds the per-logit rule).  The repetition window is the c0 codes of an utterance's last
-// min(frame, context) frames, read from the code history; C0_WINDOW_MAX is the device cap of context.
+// min(its own frame index, context) frames, read from the code history (a ring over the global frame index);
+// C0_WINDOW_MAX is the device cap of context.
 constexpr int C0_WINDOW_MAX = 256;
 struct C0ProcessParams {
   float* logits;       // [B][ls], transformed in place
@@ -275,8 +277,9 @@ struct C0ProcessParams {
   float penalty;       // 0: no repetition penalty
   int context;
   const int* hist;     // [F_cap][B][K]
-  int B, K;
-  const int* frame_ctr;
+  int B, K, F_cap;
+  const int* frame_ctr;   // the global frame index (where the history is written)
+  const int* slot_frame;  // [B] each utterance's own frame index (how much of the history is its own)
 };
 void launch_c0_process(const C0ProcessParams& p, hipStream_t st);
 
@@ -286,7 +289,8 @@ struct AdvanceParams {
   int F_cap, B, K, V;
   uint8_t* done;
   int* n_frames;
-  int* frame_ctr;
+  int* frame_ctr;   // the global frame index: the history row is frame_ctr % F_cap
+  int* slot_frame;  // [B] each utterance's own frame index (EOS and n_frames count in it)
   const unsigned long long* last_part;  // greedy: partials of the last head (null: codes already final)
   int last_stride, last_n;
 };
@@ -501,11 +505,11 @@ struct DecStepXsArgs {
   unsigned long long* head_part;
   // sampled steps (temperature > 0, top-k only; needs the head in the launch): workgroup m < M samples
   // row m from the head's logits by the sampler of sampler.h (radix-select top-k threshold, Gumbel-max with
-  // the counter key(seeds[m], frame_ctr[0] * K + cb)) -> codes[m][cb] and the single partial head_part[m][0]
+  // the counter key(seeds[m], slot_frame[m] * K + cb)) -> codes[m][cb] and the single partial head_part[m][0]
   int sample, s_top_k, s_K, s_cb;
   float s_temperature;
   const uint64_t* s_seeds;
-  const int* s_frame_ctr;
+  const int* s_slot_frame;  // [M] each row's own frame index
   float* qkvp;                            // bf16 XSD_QSPLIT: [2][RMAX][QKV] the QKV K halves' partial sums, then [48][RMAX] row scales
 };
 constexpr int DEC_XSD_STAMPS = 64;

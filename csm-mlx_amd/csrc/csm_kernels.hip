@@ -33,7 +33,7 @@ __global__ __launch_bounds__(64) void embed_rows_kernel(EmbedParams p) {
   constexpr int CH = 33;
   const int m = blockIdx.x, t = threadIdx.x;
   const int ncol = p.K + 1;
-  if (p.pos_inc && blockIdx.y == 0 && t == 0) p.pos_inc[m] += 1;
+  if (p.pos_inc && blockIdx.y == 0 && t == 0 && !(p.parked && p.parked[m])) p.pos_inc[m] += 1;
   long long off = -1;  // element offset of column t's row in its table, -1 when masked
   if (t < ncol) {
     if (p.codes) {  // decode: row = [codes, 0], mask = [1]*K + [0]  (generation.py:156-161)
@@ -1049,7 +1049,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
     }
     const bool topk = p.top_k > 0 && p.top_k < V;
     const float thr = topk ? topk_threshold<256, SAMPLE_NPT>(tid, V, p.top_k, hist, wsum, sh, RegSlots<SAMPLE_NPT>{lv}) : -INFINITY;
-    const uint64_t key = gumbel_key(p.seeds[b], p.frame_ctr[0] * p.K + p.cb);
+    const uint64_t key = gumbel_key(p.seeds[b], p.slot_frame[b] * p.K + p.cb);
     const float inv_t = 1.0f / p.temperature;
     double best = -INFINITY;
     int bi = 0x7fffffff;
@@ -1239,7 +1239,7 @@ __global__ __launch_bounds__(256) void sample_filtered_kernel(SampleParams p) {
   for (int r = 0; r < SAMPLE_NPT; ++r)
     if (kp[r]) keep[idx[r]] = 1;
   __syncthreads();
-  const uint64_t key = gumbel_key(p.seeds[b], p.frame_ctr[0] * p.K + p.cb);
+  const uint64_t key = gumbel_key(p.seeds[b], p.slot_frame[b] * p.K + p.cb);
   const float inv_t = 1.0f / p.temperature;
   double best = -INFINITY;
   int bi = 0x7fffffff;
@@ -1283,16 +1283,21 @@ __global__ void advance_kernel(AdvanceParams p) {
   {  // one wave per utterance, lane k = codebook k (K <= 64): codes read once, history row written
      // coalesced, the all-zero test by a wave vote
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    // The history is a ring over the global frame index (the identity while a batch runs <= F_cap frames);
+    // EOS and n_frames count in the utterance's own frames sf (== f unless its slot was restarted mid-batch).
+    const int row = f % p.F_cap;
     for (int b = wave; b < p.B; b += nw) {
       const int c = lane < p.K ? p.codes[(size_t)b * p.K + lane] : 0;
-      if (lane < p.K && f < p.F_cap) p.hist[((size_t)f * p.B + b) * p.K + lane] = c;
+      if (lane < p.K) p.hist[((size_t)row * p.B + b) * p.K + lane] = c;
       const bool any = __any(c != 0);
       if (lane == 0) {
+        const int sf = p.slot_frame[b];
         if (!any && !p.done[b]) {  // EOS: all-zero frame, not emitted (generation.py:151)
           p.done[b] = 1;
-          p.n_frames[b] = f;
+          p.n_frames[b] = sf;
         }
-        if (!p.done[b]) p.n_frames[b] = f + 1;
+        if (!p.done[b]) p.n_frames[b] = sf + 1;
+        p.slot_frame[b] = sf + 1;
       }
     }
   }
@@ -1308,8 +1313,8 @@ __global__ void advance_kernel(AdvanceParams p) {
 __global__ __launch_bounds__(256) void c0_process_kernel(C0ProcessParams p) {
   __shared__ int win[C0_WINDOW_MAX];
   const int b = blockIdx.x, f = p.frame_ctr[0];
-  const int n = c0_window_n(f, p.context, p.penalty);
-  for (int j = threadIdx.x; j < n; j += 256) win[j] = c0_window_code(p.hist, f, j, b, p.B, p.K);
+  const int n = c0_window_n(min(p.slot_frame[b], f), p.context, p.penalty);  // never a predecessor's codes in the same slot
+  for (int j = threadIdx.x; j < n; j += 256) win[j] = c0_window_code_ring(p.hist, f, j, b, p.B, p.K, p.F_cap);
   __syncthreads();
   float* lg = p.logits + (size_t)b * p.ls;
   for (int v = threadIdx.x; v < p.V; v += 256) lg[v] = c0_processed(lg[v], v, p.bias, win, n, p.penalty);
@@ -1532,6 +1537,7 @@ void launch_c0_process(const C0ProcessParams& p, hipStream_t st) {
 
 void launch_advance(const AdvanceParams& p, hipStream_t st) {
   if (p.K > 64) throw CsmError(CSM_ERR_ARG, "advance: at most 64 codebooks");
+  if (p.F_cap <= 0) throw CsmError(CSM_ERR_ARG, "advance: no frame history");
   hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(256), 0, st, p);
 }
 

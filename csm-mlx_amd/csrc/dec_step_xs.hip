@@ -763,7 +763,7 @@ __device__ __forceinline__ void role_s(Ctx& c) {
   const DecStepXsArgs& p = c.p;
   const int m = c.w, V = p.n_valid;
   // the Gumbel noise does not depend on the logits: drawn before the wait
-  const uint64_t key = gumbel_key(p.s_seeds[m], p.s_frame_ctr[0] * p.s_K + p.s_cb);
+  const uint64_t key = gumbel_key(p.s_seeds[m], p.s_slot_frame[m] * p.s_K + p.s_cb);
   double gn[NPT];
 #pragma unroll
   for (int i = 0; i < NPT; ++i) {

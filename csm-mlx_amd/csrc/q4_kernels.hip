@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void embed_rows_q4_kernel(EmbedParams p, int n
     rows[j] = r;
   }
   __syncthreads();
-  if (p.pos_inc && threadIdx.x == 0) p.pos_inc[m] += 1;
+  if (p.pos_inc && threadIdx.x == 0 && !(p.parked && p.parked[m])) p.pos_inc[m] += 1;
   const size_t Na = (size_t)p.V * p.K;
   float* out = p.out + (size_t)m * p.D;
   for (int d0 = threadIdx.x * 8; d0 < p.D; d0 += blockDim.x * 8) {

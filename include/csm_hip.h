@@ -149,6 +149,28 @@ int csm_frame_forced(csm_engine* e, const int32_t* codes, float* c0_logits, floa
 /* hist [F][B][K] int32 of the frames generated so far, n_frames[B] emitted frames (EOS excluded),
  * done[B].  Any pointer may be NULL. */
 int csm_read_codes(csm_engine* e, int32_t* hist, int32_t* n_frames, uint8_t* done, int* frames_run);
+/* Continuous batching (no reference counterpart: the reference runs one utterance per call).  The B rows of
+ * the batch csm_begin started are slots: each holds at most one utterance, and at any frame boundary (between
+ * two csm_run_frames calls) a slot can start a new utterance or be parked while the others go on.  An
+ * utterance's codes depend only on its prompt, its seed, the sampler and the processors -- not on the slot,
+ * on when it joined, on the other slots or on what ran in the slot before.  The first slot call after
+ * csm_begin puts the engine in slot mode; csm_begin leaves it.  In slot mode the code history is a ring of
+ * max_frames frames, so a session may run any number of frames while no single utterance exceeds max_frames.
+ *   csm_slot_restart  slot b starts a new utterance: the pending backbone row of the batch runs first (the
+ *                     other slots' last frame reaches their KV caches), then slot b's position, frame
+ *                     counters, done flag and codes are cleared and its seed set.  Follow with csm_prefill(b)
+ *                     or one csm_prefill_batch for all the slots restarted at this boundary.
+ *   csm_slot_release  slot b holds no utterance: it is parked (position 0, done set); its rows still run in
+ *                     every frame but touch nothing outside the slot.
+ *   csm_slot_read     codes [n][K] of slot b's utterance (EOS excluded; cap_frames = rows the buffer holds,
+ *                     CSM_ERR_ARG when it is too small), *n_frames and *done; any pointer may be NULL.
+ * CSM_ERR_STATE: b >= B; a restart between csm_frame_c0_logits and csm_frame_finish; running frames while a
+ * restarted slot has no prompt; frames that would take an utterance past max_frames;
+ * csm_read_codes(hist != NULL), csm_frame_c0_logits and csm_frame_forced in slot mode (csm_read_codes still
+ * polls n_frames and done). */
+int csm_slot_restart(csm_engine* e, int b, uint64_t seed);
+int csm_slot_release(csm_engine* e, int b);
+int csm_slot_read(csm_engine* e, int b, int32_t* codes, int cap_frames, int* n_frames, uint8_t* done);
 /* Debug / parity taps: "h_last" [B][D], "c0_logits" [B][Vpad], "ci_logits" [K-1][B][Vpad], "codes" [B][K],
  * "audio_head" [K-1][Vpad][Dd] (f32 or bf16 bits),
  * "weight:<MLX name>" a whole (unfused) Linear / Embedding matrix in its device layout (int4: nibbles
