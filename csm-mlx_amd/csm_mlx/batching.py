@@ -11,12 +11,17 @@ joined, on who ran beside it or on what ran in the slot before.
 No reference counterpart: the reference speaks one sentence per ``stream_generate`` call
 (run_streaming_csm_mlx.py ``tts_worker``); this is what a server with several such conversations on one
 GPU puts between them and the engine.
+
+``SlotBatch.stream`` is the same loop with audio coming out while it runs: each slot has its own streaming
+Mimi decoder state (mimi_slot_reset / mimi_decode_slots, csrc/mimi_engine.hip), a chunk of frames is decoded
+for every slot in one codec pass that reads the codes from the engine's ring history on the device, and the
+PCM of chunk c is handed out per utterance while chunk c + 1 runs on the engine's stream.
 """
 from __future__ import annotations
 
 import collections
 import ctypes
-from typing import Callable, Generator, List, Optional, Sequence, Tuple
+from typing import Callable, Generator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -27,6 +32,15 @@ from .models import CSM
 from .sampling import HostSampler, Sampler
 
 DEFAULT_CHUNK = 8
+
+
+class StreamChunk(NamedTuple):
+    """One event of ``SlotBatch.stream``: the ``len(pcm) // 1920`` new frames of utterance ``ticket``.
+    ``final`` marks the utterance's last event, which alone carries its ``codes`` (F, K) int32."""
+    ticket: int
+    pcm: np.ndarray
+    final: bool
+    codes: Optional[np.ndarray] = None
 
 
 class _EngineSlots:
@@ -50,10 +64,23 @@ class _EngineSlots:
     def prefill(self, items: Sequence[Tuple[int, np.ndarray, np.ndarray]]):
         self.cache.prefill_batch(items)
 
-    def run(self, nframes: int):
+    def run(self, nframes: int, sync: bool = True):
         """nframes frames for every slot, waited for (the wait also checks the persistent kernels'
-        hand-off error flags: all three)."""
-        self.cache.run(nframes, sync=True)
+        hand-off error flags: all three); ``sync=False``: enqueued only, ``wait`` does the rest."""
+        self.cache.run(nframes, sync=sync)
+
+    def wait(self):
+        """Wait for the enqueued frames and check the three hand-off error flags, as ``run`` does."""
+        self.cache._check()
+        _lib.check(self.L.csm_synchronize(self.model.engine))
+
+    def ring(self) -> Tuple[int, int, int]:
+        """(device pointer of the code history [F_cap][B][K], F_cap, global frames run): frame g of the
+        session is ring row g % F_cap."""
+        self.cache._check()
+        p = ctypes.c_void_p()
+        _lib.check(self.L.csm_codes_device_ptr(self.model.engine, ctypes.byref(p)))
+        return int(p.value), int(self.model.max_frames), int(self.cache.frames)
 
     def poll(self) -> Tuple[np.ndarray, np.ndarray]:
         """(n_frames [B], done [B]) of the slots' current utterances."""
@@ -93,7 +120,9 @@ class SlotBatch:
     The sampler runs on the GPU, and so must the processors (``device_processors``): a ``HostSampler`` or
     any other processor list pauses every frame for the host and has nothing to batch -- ``ValueError``.
     Creating a SlotBatch supersedes older ``FrameCache``s (and SlotBatches) of the model exactly as a new
-    ``FrameCache`` does."""
+    ``FrameCache`` does.
+
+    ``stream`` is ``run`` with audio: it yields each utterance's PCM chunk by chunk while the queue runs."""
 
     def __init__(self, model, slots: int, *, sampler, logits_processors: Optional[List[Callable]] = None,
                  chunk: int = DEFAULT_CHUNK, _engine=None):
@@ -117,6 +146,7 @@ class SlotBatch:
         self._queue: collections.deque = collections.deque()
         self._active: List[Optional[_Job]] = [None] * slots
         self._parked = [False] * slots
+        self._joined: List[int] = []     # the slots the last ``_fill`` restarted
         self._tickets = 0
 
     def submit(self, tokens, mask, max_audio_frames: int, seed: int = 0) -> int:
@@ -141,6 +171,7 @@ class SlotBatch:
         batched prefill); slots left without work are parked."""
         K = self.model.n_audio_codebooks
         joins = []
+        self._joined = []
         for b in range(self.slots):
             if self._active[b] is not None:
                 continue
@@ -152,6 +183,7 @@ class SlotBatch:
                 self._active[b] = job
                 self._parked[b] = False
                 joins.append((b, job.tokens, job.mask))
+                self._joined.append(b)
             elif not self._parked[b]:
                 self._eng.release(b)
                 self._parked[b] = True
@@ -175,6 +207,86 @@ class SlotBatch:
                     codes = self._eng.read(b, job.cap)
                     self._active[b] = None
                     yield job.ticket, codes
+
+
+    def stream(self, codec=None) -> Generator[StreamChunk, None, None]:
+        """``run`` with audio: yields ``StreamChunk(ticket, pcm, final, codes)`` as the frames of each
+        utterance are decoded -- ``pcm`` the (v * 1920,) float32 samples of its v >= 0 new frames, ``final``
+        on its last event, which also carries its codes (F, K).  The concatenated ``pcm`` of a ticket is what
+        ``stream_generate`` yields for that utterance alone; an utterance without frames gives one empty
+        final event.
+
+        Chunk c + 1 is enqueued on the engine's stream, then chunk c is decoded on the codec's (one
+        ``decode_slots`` pass for all slots, codes read from the engine's ring history on the device) and its
+        events yielded, then chunk c + 1 is waited for and polled.  A slot restarted at a boundary has its
+        codec state reset (``slot_reset``) after the decode of the chunk that holds its previous utterance's
+        last frames and before the decode of the first chunk of the new one: the resets travel with the
+        chunk record.  ``codec``: default the registered audio tokenizer of the model's codebook count."""
+        K = self.model.n_audio_codebooks
+        if codec is None:
+            from .tokenizers import get_audio_tokenizer
+            codec = get_audio_tokenizer(K)
+        if 2 * self.chunk > self.max_frames:    # a chunk's ring rows must outlive the next chunk
+            raise ValueError(f"streaming needs 2 * chunk <= max_frames: chunk {self.chunk}, the engine's code "
+                             f"history holds {self.max_frames} frames")
+        if codec.max_batch < self.slots:
+            raise ValueError(f"the codec serves {codec.max_batch} streams, the batch has {self.slots} slots "
+                             f"(MimiCodec(..., max_batch=))")
+        cap = max([j.cap for j in self._queue] + [j.cap for j in self._active if j is not None] + [0])
+        if codec.max_frames < cap:
+            raise ValueError(f"the codec holds streams of {codec.max_frames} frames, the longest utterance may "
+                             f"take {cap} (MimiCodec(..., max_frames=))")
+        fs = int(codec.m.frame_size)
+        empty = np.zeros((0,), np.float32)
+
+        def events(rec):
+            """Decode one finished chunk and yield its utterances' events."""
+            for b in rec["resets"]:
+                codec.slot_reset(b)
+            rows = rec["rows"]           # (slot, ticket, valid frames, final, codes)
+            pcm = None
+            if any(v > 0 for _, _, v, _, _ in rows):
+                active = np.zeros(self.slots, bool)
+                active[[b for b, _, _, _, _ in rows]] = True
+                pcm = codec.decode_slots(rec["ptr"], rec["n"], rec["first_row"], active, F_cap=rec["F_cap"],
+                                         on_device=True)
+            for b, ticket, v, final, codes in rows:
+                yield StreamChunk(ticket, pcm[b, : v * fs].copy() if v > 0 else empty, final, codes)
+
+        prev = None
+        delivered = [0] * self.slots         # frames of the slot's current utterance already in a chunk record
+        while True:
+            for ticket, codes in self._fill():                      # cap 0: nothing to generate
+                yield StreamChunk(ticket, empty, True, codes)
+            for b in self._joined:
+                delivered[b] = 0
+            resets = list(self._joined)
+            active = [j for j in self._active if j is not None]
+            if not active:
+                break
+            n = min(self.chunk, min(j.cap - j.ran for j in active))
+            ptr, F_cap, g0 = self._eng.ring()
+            self._eng.run(n, sync=False)
+            if prev is not None:
+                yield from events(prev)
+            self._eng.wait()
+            n_frames, done = self._eng.poll()
+            rows = []
+            for b, job in enumerate(self._active):
+                if job is None:
+                    continue
+                job.ran += n
+                final = bool(done[b]) or job.ran >= job.cap
+                valid = max(0, min(n, int(n_frames[b]) - delivered[b]))
+                delivered[b] += valid
+                codes = None
+                if final:
+                    codes = self._eng.read(b, job.cap)
+                    self._active[b] = None
+                rows.append((b, job.ticket, valid, final, codes))
+            prev = {"resets": resets, "rows": rows, "ptr": ptr, "F_cap": F_cap, "first_row": g0 % F_cap, "n": n}
+        if prev is not None:
+            yield from events(prev)
 
 
 def generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], max_audio_length_ms: float = 10_000,
@@ -203,3 +315,24 @@ def generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]],
         hist[: len(c), i] = c
     pcm = _decode_batch(model, hist, n_frames)
     return (codes, pcm) if with_codes else pcm
+
+
+def stream_generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]],
+                          max_audio_length_ms: float = 10_000, *, slots: int, temperature: float = 0.0,
+                          top_k: int = 0, sampler=None, seeds=None, max_audio_frames: Optional[Sequence[int]] = None,
+                          logits_processors: Optional[List[Callable]] = None, chunk: int = DEFAULT_CHUNK
+                          ) -> Generator[Tuple[int, np.ndarray, bool], None, None]:
+    """``generate_queue`` as a stream: yields ``(prompt index, pcm, final)`` while the queue runs -- ``pcm``
+    the new (v * 1920,) float32 samples of that prompt's utterance (v >= 0), ``final`` on its last event.  The
+    concatenation per prompt is what ``stream_generate`` yields for it alone.  The registered audio tokenizer
+    needs ``max_batch >= slots`` and ``max_frames >=`` the largest frame cap."""
+    smp = _resolve_sampler(temperature, sampler, top_k)
+    n = len(prompts)
+    caps = [int(max_audio_length_ms / 80)] * n if max_audio_frames is None else [int(c) for c in max_audio_frames]
+    if len(caps) != n:
+        raise ValueError("need one frame cap per prompt")
+    seed_list = _seed_list(seeds, n)
+    batch = SlotBatch(model, slots, sampler=smp, logits_processors=logits_processors, chunk=chunk)
+    index = {batch.submit(t, m, caps[i], int(seed_list[i])): i for i, (t, m) in enumerate(prompts)}
+    for ev in batch.stream():
+        yield index[ev.ticket], ev.pcm, ev.final

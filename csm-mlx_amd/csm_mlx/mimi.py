@@ -41,6 +41,7 @@ class MimiCodec:
         t = mimi_rope_table(m, n_pos)
         _lib.check(L.mimi_set_rope_table(h, _lib.ptr(t), t.shape[0], t.shape[1] * 2))
         self._stream_B = None
+        self._slots = False    # slot mode (slot_reset): decode_step is refused, not silently reset
 
     def __del__(self):
         try:
@@ -139,6 +140,7 @@ class MimiCodec:
             _lib.check(_lib.lib().mimi_decode(self._h, nb, F, _lib.ptr(cb), 0, 0, _lib.ptr(pcm), 0))
             out.append(pcm)
         self._stream_B = None
+        self._slots = False
         return np.concatenate(out, 0)[:, None, :]
 
     def debug_rows(self) -> np.ndarray:
@@ -154,6 +156,7 @@ class MimiCodec:
     def reset_state(self, batch_size: int = 1):
         _lib.check(_lib.lib().mimi_reset_state(self._h, batch_size))
         self._stream_B = batch_size
+        self._slots = False
 
     def decode_step(self, codes: np.ndarray) -> np.ndarray:
         """One frame: (B, n_q, 1) or (B, n_q) -> (B, 1, frame_size)."""
@@ -161,9 +164,41 @@ class MimiCodec:
         if c.ndim == 3:
             c = c[:, :, 0]
         B = c.shape[0]
-        if self._stream_B != B:
+        if self._stream_B != B and not self._slots:
             self.reset_state(B)
         c = np.ascontiguousarray(c)
         pcm = np.zeros((B, self.m.frame_size), np.float32)
         _lib.check(_lib.lib().mimi_decode_step(self._h, B, _lib.ptr(c), _lib.ptr(pcm)))
         return pcm[:, None, :]
+
+    # ------------------------------------------------------------------ slot streaming
+    def slot_reset(self, b: int):
+        """Row b of the streaming state starts a new stream (mimi_slot_reset; enqueued, not waited for).  The
+        first call puts the codec in slot mode, ``reset_state`` and ``decode`` leave it."""
+        _lib.check(_lib.lib().mimi_slot_reset(self._h, int(b)))
+        self._stream_B = None
+        self._slots = True
+
+    def decode_slots(self, hist, n: int, first_row: int, active, F_cap: Optional[int] = None,
+                     on_device: bool = False) -> np.ndarray:
+        """n frames of every slot in one pass (mimi_decode_slots): codes from the ring ``hist``
+        (F_cap, B, n_q) int32 -- a numpy array, or with ``on_device`` a device pointer in that layout (the
+        engine's code history) -- at rows (first_row + f) % F_cap.  ``active`` (B,): the slots whose streams
+        advance.  Returns (B, n * frame_size) float32; an inactive slot's row is not audio."""
+        act = np.ascontiguousarray(np.asarray(active).astype(bool), np.uint8)
+        B = act.shape[0]
+        if on_device:
+            if F_cap is None:
+                raise ValueError("decode_slots(on_device=True) needs F_cap")
+            src = ctypes.c_void_p(int(hist))
+        else:
+            ring = np.ascontiguousarray(hist, np.int32)
+            if ring.ndim != 3 or ring.shape[1] != B or ring.shape[2] != self.m.n_q:
+                raise ValueError(f"expected a ring (F_cap, {B}, {self.m.n_q}), got {ring.shape}")
+            if F_cap is not None and F_cap != ring.shape[0]:
+                raise ValueError(f"F_cap {F_cap} differs from the ring's {ring.shape[0]} rows")
+            F_cap, src = ring.shape[0], _lib.ptr(ring)
+        pcm = np.zeros((B, max(int(n), 0) * self.m.frame_size), np.float32)
+        _lib.check(_lib.lib().mimi_decode_slots(self._h, B, int(n), src, 1 if on_device else 0, int(F_cap),
+                                                int(first_row), _lib.ptr(act), _lib.ptr(pcm)))
+        return pcm

@@ -6,7 +6,9 @@
 
 enum { WDT_F32 = 0, WDT_BF16 = 1, WDT_Q4 = 2 };  // WDT_Q4: MLX affine int4, group 64 (common.h layout)
 enum { EPI_STORE = 0, EPI_ADD = 1, EPI_SILU_MUL = 2, EPI_QKV = 3, EPI_GELU = 4, EPI_ARGMAX = 5 };
-enum { ATTN_CAUSAL = 0, ATTN_WINDOW = 1, ATTN_BLOCK = 2 };
+// ATTN_FRAMES: ATTN_BLOCK applied to each run of AttnParams::blk rows of an utterance (the codec's slot
+// decode: several frames in one call, each seeing only its own frame's keys and `window` past ones)
+enum { ATTN_CAUSAL = 0, ATTN_WINDOW = 1, ATTN_BLOCK = 2, ATTN_FRAMES = 3 };
 
 // MFMA-path state owned by one engine (csm_engine::ws): split-K slice partials and arrival tickets,
 // sized by gemm_reserve outside graph capture, and the fragment-tiled copy of every weight matrix
@@ -244,6 +246,7 @@ struct AttnParams {
   void* xs_out;
   int xs_K;
   float* hs_out;
+  int blk;  // ATTN_FRAMES: rows per frame (the codec's downsample_stride)
 };
 
 struct SampleParams {

@@ -576,6 +576,10 @@ __device__ __forceinline__ void attn_block(const AttnParams& p, int m, int kvh, 
   } else if (p.mode == ATTN_WINDOW) {
     k0 = max(0, pos - p.window + 1);
     k1 = pos;
+  } else if (p.mode == ATTN_FRAMES) {  // ATTN_BLOCK per frame of blk rows: a later frame of the call stays unseen
+    const int off = pos - (m % p.rm.T) % p.blk;
+    k0 = max(0, off - p.window);
+    k1 = off + p.blk - 1;
   } else {  // ATTN_BLOCK: moshi_mlx -- every key of the call visible, past trimmed to `window`
     const int off = pos - (m % p.rm.T);
     k0 = max(0, off - p.window);

@@ -95,6 +95,11 @@ struct mimi_codec {
   std::vector<float*> hist;  // per decoder op input history [B_max][cin][pad]
   float* up_hist = nullptr;  // [B_max][dim][1]
   std::vector<int> hist_pad;
+  // slot mode (mimi_slot_reset / mimi_decode_slots): every row of the streaming state is a slot with its own
+  // latent position (device; the host mirror serves the capacity check only)
+  bool slot_mode = false;
+  int* slot_pos = nullptr;  // [B_max]
+  std::vector<int> slot_pos_host;
 
   void* alloc(size_t bytes) {
     void* p = nullptr;
@@ -326,13 +331,15 @@ LinParams lin_params(mimi_codec* m, const float* x, int M, int K, const float* W
   return lp;
 }
 
-// x rows [M = B*T][D] in place through the codec transformer; positions offset..offset+T-1
+// x rows [M = B*T][D] in place through the codec transformer; positions offset..offset+T-1, or with slot_pos
+// (device, [B]) utterance b's at slot_pos[b]..slot_pos[b]+T-1: the T rows are then T / downsample_stride frames
+// of one call, and in the moshi_mlx mode each sees the keys a decode_step call of its own would (ATTN_FRAMES)
 void run_transformer(mimi_codec* m, std::vector<MTLayer>& T, std::vector<float*>& kc, std::vector<float*>& vc, int B,
-                     int Tn, int offset) {
+                     int Tn, int offset, const int* slot_pos = nullptr) {
   const mimi_dims& d = m->d;
   const int D = d.dimension, M = B * Tn, H = d.num_heads, hd = m->hd, F = d.dim_feedforward;
   hipStream_t st = m->st;
-  RowMap rm{Tn, 0, nullptr, offset};
+  RowMap rm{Tn, 0, slot_pos, offset};
   for (size_t l = 0; l < T.size(); ++l) {
     MTLayer& L = T[l];
     launch_layernorm_rows(m->R, D, L.n1w, L.n1b, d.norm_eps, m->Rh, M, st);
@@ -341,8 +348,10 @@ void run_transformer(mimi_codec* m, std::vector<MTLayer>& T, std::vector<float*>
     AttnParams a{};
     a.q = m->Rq; a.qs = D; a.M = M; a.kc = kc[l]; a.vc = vc[l]; a.Hq = H; a.Hkv = H; a.S_cap = m->S_cap;
     a.scale = 1.0f / sqrtf((float)hd); a.window = d.context; a.rm = rm; a.out = m->Ratt; a.os = D;
-    a.mode = d.attn_mode == 0 ? ATTN_BLOCK : ATTN_WINDOW;
+    a.mode = d.attn_mode != 0 ? ATTN_WINDOW : (slot_pos ? ATTN_FRAMES : ATTN_BLOCK);
+    a.blk = d.downsample_stride;
     launch_attn(a, hd, st);
+    mimi_count_launch();
     launch_linear(lin_params(m, m->Ratt, M, D, L.out_w, D, m->R, EPI_ADD, L.ls1), st);
     launch_layernorm_rows(m->R, D, L.n2w, L.n2b, d.norm_eps, m->Rh, M, st);
     LinParams up = lin_params(m, m->Rh, M, D, L.l1, F, m->Rf, EPI_GELU);
@@ -523,6 +532,8 @@ int mimi_create(const mimi_dims* dims, int device, int max_batch, int max_frames
       m->hist.push_back(P > 0 ? (float*)m->alloc((size_t)max_batch * m->op_cin(o) * P * 4) : nullptr);
     }
     m->up_hist = (float*)m->alloc((size_t)max_batch * dims->dimension * 4);
+    m->slot_pos = (int*)m->alloc((size_t)max_batch * 4);
+    m->slot_pos_host.assign(max_batch, 0);
     m->ks_ws = (float*)m->alloc(MIMI_KS_WS_FLOATS * 4);
     HIPCHK(hipDeviceSynchronize());
     *out = m.release();
@@ -704,19 +715,21 @@ int mimi_encode_rows(mimi_codec* m, int B, int N, const float* pcm, const float*
   CSM_CATCH
 }
 
-static void decode_frames(mimi_codec* m, int B, int F, const int32_t* dcodes, int layout, bool stream) {
+// slots: the rows are slots at their own positions (m->slot_pos), the codes layout 2's ring
+static void decode_frames(mimi_codec* m, int B, int F, const int32_t* dcodes, int layout, bool stream,
+                          bool slots = false, int first_row = 0, int F_cap = 0) {
   const mimi_dims& d = m->d;
   hipStream_t st = m->st;
   const int D = d.dimension, cd = d.codebook_dim, s = d.downsample_stride;
   const int n_lat = F * s;
   const int M = B * F;
   // RVQ decode: semantic + acoustic gathers, output projections summed into conv layout [B][D][F]
-  launch_rvq_gather(dcodes, layout, B, F, d.n_q, 0, 1, m->cb, d.bins, cd, m->Rh, st);
+  launch_rvq_gather(dcodes, layout, B, F, d.n_q, 0, 1, m->cb, d.bins, cd, m->Rh, st, first_row, F_cap);
   LinParams lp = lin_params(m, m->Rh, M, cd, m->rvq_out[0], D, m->W1);
   lp.conv_T = F; lp.conv_bstride = D * F;
   launch_linear(lp, st);
   if (d.n_q > 1) {
-    launch_rvq_gather(dcodes, layout, B, F, d.n_q, 1, d.n_q, m->cb, d.bins, cd, m->Rh, st);
+    launch_rvq_gather(dcodes, layout, B, F, d.n_q, 1, d.n_q, m->cb, d.bins, cd, m->Rh, st, first_row, F_cap);
     lp.W = m->rvq_out[1];
     lp.accumulate = 1;
     launch_linear(lp, st);
@@ -733,8 +746,12 @@ static void decode_frames(mimi_codec* m, int B, int F, const int32_t* dcodes, in
   launch_upsample_dw(m->H, B, D, D * cs, cs, 0, m->up_w, s, 1, F, m->W1, D * n_lat, n_lat, 0, st);
   // transformer on the latent steps
   launch_conv_to_rows(m->W1, B, D, n_lat, D * n_lat, n_lat, 0, m->R, st);
-  run_transformer(m, m->dtr, m->dkc, m->dvc, B, n_lat, m->s_off);
-  m->s_off += n_lat;
+  if (slots) {
+    run_transformer(m, m->dtr, m->dkc, m->dvc, B, n_lat, 0, m->slot_pos);
+  } else {
+    run_transformer(m, m->dtr, m->dkc, m->dvc, B, n_lat, m->s_off);
+    m->s_off += n_lat;
+  }
   m->r_rows = (size_t)B * n_lat;  // R: the decoder transformer's output, read only from here on
   const int P0 = m->op_pad(m->dec_ops[0]);
   launch_rows_to_conv(m->R, B, D, n_lat, m->W0, D * (P0 + n_lat), P0 + n_lat, P0, st);
@@ -752,7 +769,9 @@ int mimi_decode(mimi_codec* m, int B, int F, const int32_t* codes, int codes_on_
     const size_t per = decoder_ws(m, F * s);
     ensure_ws(m, per * B + 64, (size_t)B * F * s + 8);
     // Mimi.decode resets the decoder state first (moshi_mlx), so a one-shot decode starts at position 0
+    // (and writes the decoder KV of rows 0..B-1 from there: the slots' streams end here)
     m->s_off = 0;
+    m->slot_mode = false;
     const int32_t* dc = codes;
     if (!codes_on_device) {
       grow(m->dcodes, m->dcodes_n, (size_t)B * d.n_q * F);
@@ -776,6 +795,7 @@ int mimi_reset_state(mimi_codec* m, int B) {
     HIPCHK(hipSetDevice(m->dev));
     m->s_B = B;
     m->s_off = 0;
+    m->slot_mode = false;
     for (size_t i = 0; i < m->hist.size(); ++i)
       if (m->hist[i])
         HIPCHK(hipMemsetAsync(m->hist[i], 0, (size_t)B * m->op_cin(m->dec_ops[i]) * m->hist_pad[i] * 4, m->st));
@@ -787,6 +807,8 @@ int mimi_reset_state(mimi_codec* m, int B) {
 
 int mimi_decode_step(mimi_codec* m, int B, const int32_t* codes, float* pcm) {
   CSM_TRY {
+    if (m->slot_mode)
+      throw CsmError(CSM_ERR_STATE, "the codec is in slot mode (mimi_slot_reset): mimi_reset_state(B) leaves it");
     if (B != m->s_B) throw CsmError(CSM_ERR_STATE, "mimi_reset_state(B) must precede decode_step");
     const int s = m->d.downsample_stride;
     if (m->s_off + s + 4 > m->S_cap) throw CsmError(CSM_ERR_ARG, "stream longer than the codec capacity");
@@ -804,10 +826,97 @@ int mimi_decode_step(mimi_codec* m, int B, const int32_t* codes, float* pcm) {
   CSM_CATCH
 }
 
+// Slot b's streaming state zeroed and its position set to 0 (b < 0: every slot's): one launch, no wait
+static void slot_reset_launch(mimi_codec* m, int b) {
+  MimiSlotResetParams p{};
+  for (size_t i = 0; i < m->hist.size(); ++i) {
+    if (!m->hist[i]) continue;
+    if (p.n >= MIMI_SLOT_BUFS - 1) throw CsmError(CSM_ERR_ARG, "codec with more streaming buffers than the slot reset table");
+    p.buf[p.n] = m->hist[i];
+    p.per[p.n++] = m->op_cin(m->dec_ops[i]) * m->hist_pad[i];
+  }
+  p.buf[p.n] = m->up_hist;
+  p.per[p.n++] = m->d.dimension;
+  p.slot_pos = m->slot_pos; p.b = b; p.B = m->B_max;
+  launch_mimi_slot_reset(p, m->st);
+  HIPCHK(hipGetLastError());
+  if (b < 0) std::fill(m->slot_pos_host.begin(), m->slot_pos_host.end(), 0);
+  else m->slot_pos_host[b] = 0;
+}
+
+int mimi_slot_reset(mimi_codec* m, int b) {
+  CSM_TRY {
+    if (!m) throw CsmError(CSM_ERR_ARG, "null codec");
+    if (b < 0 || b >= m->B_max) throw CsmError(CSM_ERR_ARG, "codec slot index out of range");
+    if (m->B_max > MIMI_SLOTS_MAX) throw CsmError(CSM_ERR_ARG, "a slot-mode codec serves at most 256 slots");
+    HIPCHK(hipSetDevice(m->dev));
+    if (!m->slot_mode) {  // the first reset since mimi_reset_state / creation: every row starts as an idle slot
+      m->slot_mode = true;
+      m->s_B = 0;
+      slot_reset_launch(m, -1);
+    } else {
+      slot_reset_launch(m, b);
+    }
+  }
+  CSM_CATCH
+}
+
+int mimi_decode_slots(mimi_codec* m, int B, int n, const int32_t* hist, int codes_on_device, int F_cap, int first_row,
+                      const uint8_t* active, float* pcm) {
+  CSM_TRY {
+    if (!m || !hist || !active || !pcm) throw CsmError(CSM_ERR_ARG, "null codec, history, active mask or pcm");
+    if (!m->slot_mode) throw CsmError(CSM_ERR_STATE, "mimi_slot_reset must precede mimi_decode_slots");
+    if (B <= 0 || B > m->B_max) throw CsmError(CSM_ERR_ARG, "bad slot count");
+    if (F_cap < 1 || n < 1 || n > F_cap) throw CsmError(CSM_ERR_ARG, "bad frame count for the ring history");
+    if (first_row < 0 || first_row >= F_cap) throw CsmError(CSM_ERR_ARG, "first ring row out of range");
+    const mimi_dims& d = m->d;
+    const int s = d.downsample_stride, steps = n * s;
+    if (steps + 4 > m->S_cap) throw CsmError(CSM_ERR_ARG, "more frames than the codec capacity");
+    for (int b = 0; b < B; ++b)
+      if (active[b] && m->slot_pos_host[b] + steps + 4 > m->S_cap)
+        throw CsmError(CSM_ERR_ARG, "slot " + std::to_string(b) + ": stream longer than the codec capacity");
+    HIPCHK(hipSetDevice(m->dev));
+    // an idle row still flows through the pass at its own position: one whose last stream stopped near the
+    // end of the cache goes back to 0 first (it starts its next stream with a reset anyway)
+    for (int b = 0; b < B; ++b)
+      if (!active[b] && m->slot_pos_host[b] + steps + 4 > m->S_cap) slot_reset_launch(m, b);
+    const size_t per = decoder_ws(m, steps);
+    ensure_ws(m, per * B + 64, (size_t)B * steps + 8);
+    const int32_t* dc = hist;
+    if (!codes_on_device) {
+      const size_t ring = (size_t)F_cap * B * d.n_q;
+      grow(m->dcodes, m->dcodes_n, ring);
+      HIPCHK(hipMemcpyAsync(m->dcodes, hist, ring * 4, hipMemcpyHostToDevice, m->st));
+      dc = m->dcodes;
+    }
+    decode_frames(m, B, n, dc, 2, true, true, first_row, F_cap);
+    MimiSlotMask mask{};
+    for (int b = 0; b < B; ++b) {
+      mask.v[b] = active[b] ? 1 : 0;
+      if (active[b]) m->slot_pos_host[b] += steps;
+    }
+    launch_mimi_slot_advance(m->slot_pos, mask, B, steps, m->st);
+    const Pcm out = decoder_pcm(m, steps);
+    HIPCHK(hipMemcpyAsync(pcm, out.p, (size_t)B * out.n * 4, hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipStreamSynchronize(m->st));
+    HIPCHK(hipGetLastError());
+  }
+  CSM_CATCH
+}
+
 int mimi_debug_read(mimi_codec* m, const char* what, void* host, int64_t nbytes, int64_t* needed) {
   CSM_TRY {
     if (!m || !what) throw CsmError(CSM_ERR_ARG, "bad mimi_debug_read arguments");
     const std::string w(what);
+    if (w == "launches") {  // the process-wide host counter of codec kernel launches, one int64
+      if (needed) *needed = 8;
+      if (host) {
+        if (nbytes < 8) throw CsmError(CSM_ERR_ARG, "debug buffer too small");
+        const long long v = mimi_kernel_launches();
+        memcpy(host, &v, 8);
+      }
+      return CSM_OK;
+    }
     if (w != "rows") throw CsmError(CSM_ERR_ARG, "unknown codec debug tap " + w);
     if (!m->R || !m->r_rows) throw CsmError(CSM_ERR_STATE, "no encode / decode call has run yet");
     HIPCHK(hipSetDevice(m->dev));

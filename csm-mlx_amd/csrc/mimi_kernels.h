@@ -94,10 +94,11 @@ void launch_rope_append(const float* qkv, int M, int D, int H, int hd, const flo
 // depthwise ConvTranspose k=2s (upsample): y[b][c][(ti-t_in0)*s + r] = x[ti]*w[c][r] + x[ti-1]*w[c][r+s]
 void launch_upsample_dw(const float* x, int B, int C, int x_bstride, int x_cstride, int x_off, const float* w, int s,
                         int t_in0, int n_in, float* y, int y_bstride, int y_cstride, int y_off, hipStream_t st);
-// RVQ decode gather: q[m][cd] = sum_{k in [k0,k1)} cb[k][code(m,k)]  with codes [B][n_q][F] (layout 0)
-// or engine history [F][B][n_q] (layout 1); m = b*F + f
+// RVQ decode gather: q[m][cd] = sum_{k in [k0,k1)} cb[k][code(m,k)]  with codes [B][n_q][F] (layout 0),
+// engine history [F][B][n_q] (layout 1) or the engine's ring history [F_cap][B][n_q] read at rows
+// (first_row + f) % F_cap (layout 2); m = b*F + f
 void launch_rvq_gather(const int* codes, int layout, int B, int F, int n_q, int k0, int k1, const float* cb, int bins,
-                       int cd, float* q, hipStream_t st);
+                       int cd, float* q, hipStream_t st, int first_row = 0, int F_cap = 0);
 // RVQ encode: r[m][cd] residual (in place); for k in [k0,k1): idx = argmin(c2half - r.c), r -= c[idx];
 // codes[b][k][t] for m = b*T + t
 void launch_rvq_encode(float* r, int M, int T, int cd, const float* cb, const float* c2half, int bins, int k0, int k1,
@@ -113,3 +114,25 @@ void launch_rvq_encode_gemm(float* r, int M, int T, int cd, const float* cb, con
 // copy a [B][C][len] window: dst[b][c][i] = src[b][c][src_off + i]
 void launch_copy_window(const float* src, int B, int C, int src_bstride, int src_cstride, int src_off, float* dst,
                         int dst_bstride, int dst_cstride, int dst_off, int len, hipStream_t st);
+
+// Per-slot streaming decoder state (mimi_slot_reset / mimi_decode_slots): every streaming buffer is
+// [B_max][per] floats, slot b owning [b * per, (b + 1) * per); slot_pos[b] is the slot's latent position.
+constexpr int MIMI_SLOT_BUFS = 24;    // decoder-op histories (<= 2 + 2 * 8 ratios) + the upsample history
+constexpr int MIMI_SLOTS_MAX = 256;   // slots a slot-mode codec serves (the active mask travels as a kernel argument)
+struct MimiSlotResetParams {
+  float* buf[MIMI_SLOT_BUFS];
+  int per[MIMI_SLOT_BUFS];  // floats per slot
+  int n;                    // buffers in the table
+  int* slot_pos;
+  int b, B;                 // the slot to reset, or b < 0: all B of them
+};
+struct MimiSlotMask {
+  uint8_t v[MIMI_SLOTS_MAX];
+};
+void launch_mimi_slot_reset(const MimiSlotResetParams& p, hipStream_t st);
+// slot_pos[b] += steps where active.v[b], b < B
+void launch_mimi_slot_advance(int* slot_pos, const MimiSlotMask& active, int B, int steps, hipStream_t st);
+
+// Kernel launches the codec has made in this process (a host counter, for the launch accounting of the benches)
+long long mimi_kernel_launches();
+void mimi_count_launch();

@@ -6,9 +6,21 @@
 // Everything stays fp32 (waveform parity target: 1e-4 RMS).
 #include "mimi_kernels.h"
 
+#include <atomic>
 #include <string>
 
 #include "engine_util.h"
+
+// Host counter of the codec's kernel launches (mimi_debug_read "launches"): every launch of this file
+// goes through MIMI_LAUNCH; the codec transformer's attention launch is added by its caller.
+static std::atomic<long long> g_mimi_launches{0};
+long long mimi_kernel_launches() { return g_mimi_launches.load(std::memory_order_relaxed); }
+void mimi_count_launch() { g_mimi_launches.fetch_add(1, std::memory_order_relaxed); }
+#define MIMI_LAUNCH(...)                \
+  do {                                  \
+    mimi_count_launch();                \
+    hipLaunchKernelGGL(__VA_ARGS__);    \
+  } while (0)
 
 // ============================================================================ tiled GEMM core
 // Four consecutive floats at p as one 16-B load when p is 16-B aligned (else four 4-B loads): the
@@ -240,12 +252,12 @@ static void launch_tile(const P& pr, int Z, int ks, float* ws, hipStream_t st) {
   if (BN != 64 && ks > 1) throw CsmError(CSM_ERR_HIP, "mimi: a wide-tile plan with split-K (ks " + std::to_string(ks) + ")");
   const dim3 g((pr.N + BN - 1) / BN, (pr.M + BM - 1) / BM, Z);
   if (ks <= 1 || !ws) {
-    hipLaunchKernelGGL((gemm_mf_kernel<P, false, BM, BN>), g, dim3(256), 0, st, pr, 1, nullptr, Z);
+    MIMI_LAUNCH((gemm_mf_kernel<P, false, BM, BN>), g, dim3(256), 0, st, pr, 1, nullptr, Z);
   } else if constexpr (BN == 64) {
-    hipLaunchKernelGGL((gemm_mf_kernel<P, true, BM, BN>), dim3(g.x, g.y, g.z * ks), dim3(256), 0, st, pr, ks, ws, Z);
+    MIMI_LAUNCH((gemm_mf_kernel<P, true, BM, BN>), dim3(g.x, g.y, g.z * ks), dim3(256), 0, st, pr, ks, ws, Z);
     const size_t tot = (size_t)Z * pr.M * pr.N;
     const int rb = (int)std::min<size_t>(2048, (tot + 255) / 256);
-    hipLaunchKernelGGL(splitk_reduce_kernel<P>, dim3(rb), dim3(256), 0, st, pr, ws, ks, Z);
+    MIMI_LAUNCH(splitk_reduce_kernel<P>, dim3(rb), dim3(256), 0, st, pr, ws, ks, Z);
   }
 }
 
@@ -537,7 +549,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* x, int
 
 void launch_layernorm_rows(const float* x, int D, const float* w, const float* b, float eps, float* out, int M,
                            hipStream_t st) {
-  hipLaunchKernelGGL(layernorm_rows_kernel, dim3(M), dim3(256), 0, st, x, D, w, b, eps, out);
+  MIMI_LAUNCH(layernorm_rows_kernel, dim3(M), dim3(256), 0, st, x, D, w, b, eps, out);
 }
 
 // ============================================================================ layout transposes
@@ -549,7 +561,7 @@ __global__ void conv_to_rows_kernel(const float* x, int C, int T, int x_bstride,
 }
 void launch_conv_to_rows(const float* x, int B, int C, int T, int x_bstride, int x_cstride, int x_off, float* rows,
                          hipStream_t st) {
-  hipLaunchKernelGGL(conv_to_rows_kernel, dim3((T + 63) / 64, (C + 3) / 4, B), dim3(256), 0, st, x, C, T, x_bstride,
+  MIMI_LAUNCH(conv_to_rows_kernel, dim3((T + 63) / 64, (C + 3) / 4, B), dim3(256), 0, st, x, C, T, x_bstride,
                      x_cstride, x_off, rows);
 }
 __global__ void rows_to_conv_kernel(const float* rows, int C, int T, float* y, int y_bstride, int y_cstride,
@@ -560,7 +572,7 @@ __global__ void rows_to_conv_kernel(const float* rows, int C, int T, float* y, i
 }
 void launch_rows_to_conv(const float* rows, int B, int C, int T, float* y, int y_bstride, int y_cstride, int y_off,
                          hipStream_t st) {
-  hipLaunchKernelGGL(rows_to_conv_kernel, dim3((T + 63) / 64, (C + 3) / 4, B), dim3(256), 0, st, rows, C, T, y,
+  MIMI_LAUNCH(rows_to_conv_kernel, dim3((T + 63) / 64, (C + 3) / 4, B), dim3(256), 0, st, rows, C, T, y,
                      y_bstride, y_cstride, y_off);
 }
 
@@ -587,7 +599,7 @@ __global__ void rope_append_kernel(const float* qkv, int M, int D, int H, int hd
 }
 void launch_rope_append(const float* qkv, int M, int D, int H, int hd, const float* rope, RowMap rm, float* qout,
                         float* kc, float* vc, int S_cap, hipStream_t st) {
-  hipLaunchKernelGGL(rope_append_kernel, dim3(M), dim3(256), 0, st, qkv, M, D, H, hd, rope, rm, qout, kc, vc, S_cap);
+  MIMI_LAUNCH(rope_append_kernel, dim3(M), dim3(256), 0, st, qkv, M, D, H, hd, rope, rm, qout, kc, vc, S_cap);
 }
 
 // ============================================================================ depthwise upsample
@@ -604,7 +616,7 @@ __global__ void upsample_dw_kernel(const float* x, int C, int x_bstride, int x_c
 }
 void launch_upsample_dw(const float* x, int B, int C, int x_bstride, int x_cstride, int x_off, const float* w, int s,
                         int t_in0, int n_in, float* y, int y_bstride, int y_cstride, int y_off, hipStream_t st) {
-  hipLaunchKernelGGL(upsample_dw_kernel, dim3((n_in * s + 255) / 256, C, B), dim3(256), 0, st, x, C, x_bstride,
+  MIMI_LAUNCH(upsample_dw_kernel, dim3((n_in * s + 255) / 256, C, B), dim3(256), 0, st, x, C, x_bstride,
                      x_cstride, x_off, w, s, t_in0, n_in, y, y_bstride, y_cstride, y_off);
 }
 
@@ -613,13 +625,15 @@ void launch_upsample_dw(const float* x, int B, int C, int x_bstride, int x_cstri
 // the restated ResidualVectorQuantizer.decode accumulates them.  Ids >= bins (2048..2050, valid
 // CSM outputs but outside the Mimi codebook) are clamped to bins-1.
 __global__ void rvq_gather_kernel(const int* codes, int layout, int B, int F, int n_q, int k0, int k1,
-                                  const float* cb, int bins, int cd, float* q) {
+                                  const float* cb, int bins, int cd, float* q, int first_row, int F_cap) {
   const int m = blockIdx.x;  // b*F + f
   const int b = m / F, f = m % F;
+  // layout 2: frame f of the call is row (first_row + f) % F_cap of the engine's ring history
+  const int row = layout == 2 ? (first_row + f) % F_cap : f;
   for (int d = threadIdx.x; d < cd; d += blockDim.x) {
     float acc = 0.f;
     for (int k = k0; k < k1; ++k) {
-      int c = layout == 0 ? codes[((size_t)b * n_q + k) * F + f] : codes[((size_t)f * B + b) * n_q + k];
+      int c = layout == 0 ? codes[((size_t)b * n_q + k) * F + f] : codes[((size_t)row * B + b) * n_q + k];
       c = min(max(c, 0), bins - 1);
       acc = acc + cb[((size_t)k * bins + c) * cd + d];
     }
@@ -627,9 +641,9 @@ __global__ void rvq_gather_kernel(const int* codes, int layout, int B, int F, in
   }
 }
 void launch_rvq_gather(const int* codes, int layout, int B, int F, int n_q, int k0, int k1, const float* cb, int bins,
-                       int cd, float* q, hipStream_t st) {
-  hipLaunchKernelGGL(rvq_gather_kernel, dim3(B * F), dim3(256), 0, st, codes, layout, B, F, n_q, k0, k1, cb, bins, cd,
-                     q);
+                       int cd, float* q, hipStream_t st, int first_row, int F_cap) {
+  MIMI_LAUNCH(rvq_gather_kernel, dim3(B * F), dim3(256), 0, st, codes, layout, B, F, n_q, k0, k1, cb, bins, cd,
+                     q, first_row, F_cap);
 }
 
 // encode: one block per latent row; residual in LDS; per codebook every thread scores bins/256
@@ -842,13 +856,13 @@ void launch_rvq_encode_gemm(float* r, int M, int T, int cd, const float* cb, con
     s.cbT = k < k1 ? cbT + (size_t)k * bins * cd : nullptr;
     s.c2half = k < k1 ? c2half + (size_t)k * bins : nullptr;
     // the finishing pass needs only code tile 0 (it writes the codes and r); it computes no distances
-    hipLaunchKernelGGL(rvq_step_kernel<true>, k == k1 ? dim3(1, grid.y) : grid, dim3(256), 0, st, s);
+    MIMI_LAUNCH(rvq_step_kernel<true>, k == k1 ? dim3(1, grid.y) : grid, dim3(256), 0, st, s);
   }
 }
 
 void launch_rvq_encode(float* r, int M, int T, int cd, const float* cb, const float* c2half, int bins, int k0, int k1,
                        int n_q, int* codes, hipStream_t st) {
-  hipLaunchKernelGGL(rvq_encode_kernel, dim3(M), dim3(256), 0, st, r, T, cd, cb, c2half, bins, k0, k1, n_q, codes);
+  MIMI_LAUNCH(rvq_encode_kernel, dim3(M), dim3(256), 0, st, r, T, cd, cb, c2half, bins, k0, k1, n_q, codes);
 }
 
 // ============================================================================ window copy
@@ -862,6 +876,32 @@ __global__ void copy_window_kernel(const float* src, int src_bstride, int src_cs
 void launch_copy_window(const float* src, int B, int C, int src_bstride, int src_cstride, int src_off, float* dst,
                         int dst_bstride, int dst_cstride, int dst_off, int len, hipStream_t st) {
   if (len <= 0) return;
-  hipLaunchKernelGGL(copy_window_kernel, dim3((len + 255) / 256, C, B), dim3(256), 0, st, src, src_bstride,
+  MIMI_LAUNCH(copy_window_kernel, dim3((len + 255) / 256, C, B), dim3(256), 0, st, src, src_bstride,
                      src_cstride, src_off, dst, dst_bstride, dst_cstride, dst_off, len);
+}
+
+// ============================================================================ per-slot streaming state
+// Slot b's slice of every streaming buffer of the table zeroed (block x: buffer x, or all of them in turn
+// when the grid is one block), its latent position set to 0; b < 0: every one of the B slots.
+__global__ __launch_bounds__(256) void mimi_slot_reset_kernel(MimiSlotResetParams p) {
+  const int b0 = p.b < 0 ? 0 : p.b, nb = p.b < 0 ? p.B : 1;
+  for (int i = blockIdx.x; i < p.n; i += gridDim.x) {
+    float* dst = p.buf[i] + (size_t)b0 * p.per[i];
+    const size_t len = (size_t)nb * p.per[i];
+    for (size_t j = threadIdx.x; j < len; j += 256) dst[j] = 0.f;
+  }
+  if (blockIdx.x == 0)
+    for (int j = threadIdx.x; j < nb; j += 256) p.slot_pos[b0 + j] = 0;
+}
+void launch_mimi_slot_reset(const MimiSlotResetParams& p, hipStream_t st) {
+  MIMI_LAUNCH(mimi_slot_reset_kernel, dim3(p.n > 0 ? p.n : 1), dim3(256), 0, st, p);
+}
+
+// The end of a slot decode pass: the active slots' positions move on by the pass's latent steps
+__global__ void mimi_slot_advance_kernel(int* slot_pos, MimiSlotMask active, int B, int steps) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B && active.v[b]) slot_pos[b] += steps;
+}
+void launch_mimi_slot_advance(int* slot_pos, const MimiSlotMask& active, int B, int steps, hipStream_t st) {
+  MIMI_LAUNCH(mimi_slot_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, slot_pos, active, B, steps);
 }

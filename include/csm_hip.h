@@ -219,6 +219,28 @@ int mimi_decode(mimi_codec* m, int B, int F, const int32_t* codes, int codes_on_
 /* streaming: reset per-utterance state, then one frame at a time: codes [B][n_q] -> pcm [B][frame_size] */
 int mimi_reset_state(mimi_codec* m, int B);
 int mimi_decode_step(mimi_codec* m, int B, const int32_t* codes, float* pcm);
+/* Slot streaming (the codec's side of csm_slot_*): every row of the streaming decoder state is a slot with its
+ * own stream and its own latent position, so one slot starts a new utterance while its neighbours go on.
+ *   mimi_slot_reset    row b starts a new stream: its slice of every conv / upsample history is zeroed and
+ *                      its position set to 0 by one small launch on the codec stream (no wait).  The KV
+ *                      caches are not cleared: from position 0 on the slot reads only keys it has written
+ *                      since.  The first call after mimi_create or mimi_reset_state puts the codec in slot
+ *                      mode and clears every row once; mimi_reset_state and mimi_decode leave slot mode.
+ *                      CSM_ERR_ARG: b outside [0, max_batch), or a codec of more than 256 rows.
+ *   mimi_decode_slots  n consecutive frames of rows 0..B-1 in one pass, each slot continuing its own stream:
+ *                      codes from a ring history [F_cap][B][n_q] (csm_codes_device_ptr's layout with
+ *                      codes_on_device, the same layout in host memory without) at rows
+ *                      (first_row + f) % F_cap, f < n; pcm [B][n * frame_size] float32 host.  active[B]
+ *                      (host): an inactive row still runs (its pcm is not audio) but its position does not
+ *                      advance, and it must be reset before it carries a stream again.  Waits for the
+ *                      codec stream.  A slot's frames equal mimi_decode_step's on that stream alone,
+ *                      however the frames are split over calls.
+ *                      CSM_ERR_STATE: not in slot mode.  CSM_ERR_ARG: B > max_batch, n < 1, n > F_cap, or an
+ *                      active slot would pass the codec's capacity (refused before anything is launched).
+ * mimi_decode_step in slot mode is CSM_ERR_STATE. */
+int mimi_slot_reset(mimi_codec* m, int b);
+int mimi_decode_slots(mimi_codec* m, int B, int n, const int32_t* hist, int codes_on_device, int F_cap,
+                      int first_row, const uint8_t* active, float* pcm);
 
 #ifdef __cplusplus
 }

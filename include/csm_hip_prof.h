@@ -110,7 +110,9 @@ int mimi_lab_rvq_encode(int gemm, int M, int T, int cd, int bins, int n_q, int k
                         const float* c2half, float* r, int32_t* codes);
 /* Inspection tap of a codec: "rows" = the engine's row buffer [rows][dimension] as the last call left it:
  * after mimi_encode* the pre-RVQ latent [B * Tf][D], after mimi_decode / mimi_decode_step the decoder
- * transformer's output [B * n_lat][D].  *needed = its bytes; host NULL: size query only. */
+ * transformer's output [B * n_lat][D].  *needed = its bytes; host NULL: size query only.
+ * "launches" = one int64: the kernel launches the codec code has made in this process so far (a host
+ * counter; tools/slots_bench.py --stream divides its growth by the chunks decoded). */
 int mimi_debug_read(mimi_codec* m, const char* what, void* host, int64_t nbytes, int64_t* needed);
 
 #ifdef __cplusplus

@@ -6,7 +6,15 @@ csm_1b bf16 synthetic weights, 96 prompts, greedy, per-prompt frame caps drawn o
   static  three generate_batch calls of 32 prompts, each running to its longest member's cap
 
 Per run: useful utterance-frames/s (frames inside their utterance's cap) and the share of the slot-frames
-the engine ran that were useful.  usage: slots_bench.py [repeats]"""
+the engine ran that were useful.  usage: slots_bench.py [repeats]
+
+``slots_bench.py --stream [repeats]``: what audio costs on the same workload, alternating
+  (a) generate_queue(decode=False)          codes only
+  (b) generate_queue(decode=True)           one batched Mimi.decode per length group after the queue drained
+  (c) SlotBatch.stream at chunk 1, 2, 4, 8  PCM per utterance while the queue runs (mimi_202407, synthetic weights)
+with, for (c), the time from an utterance's join to its first PCM event (median, p95; without streaming it is
+the time to the utterance's end, printed beside it) and the codec's kernel launches per decoded chunk
+(the host counter behind mimi_debug_read "launches")."""
 import ctypes
 import os
 import sys
@@ -23,7 +31,9 @@ from csm_mlx.tokenizers import tokenize_text_segment  # noqa: E402
 from csm_mlx.weights import bf16_bits, synthetic_csm_weights  # noqa: E402
 
 N, SLOTS = 96, 32
-repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 2
+STREAM = "--stream" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--stream"]
+repeats = int(argv[0]) if argv else 2
 args = csm_1b()
 model = CSM(args, dtype="bf16", max_batch=SLOTS)
 model.load_weights({k: bf16_bits(v) for k, v in synthetic_csm_weights(args, 0).items()})
@@ -59,6 +69,99 @@ def static():
         codes += [c[:caps[i + j]] for j, c in enumerate(got)]
     return time.perf_counter() - t, ran, codes
 
+
+def stream_bench():
+    from csm_mlx import SlotBatch
+    from csm_mlx.config import MIMI_CONFIGURATION
+    from csm_mlx.mimi import MimiCodec
+    from csm_mlx.sampling import Sampler
+    from csm_mlx.tokenizers import set_audio_tokenizer
+    from csm_mlx.weights import synthetic_mimi_weights
+    mm = MIMI_CONFIGURATION["mimi_202407"]
+    codec = MimiCodec(mm, max_batch=SLOTS, max_frames=128)
+    codec.load_weights(synthetic_mimi_weights(mm))
+    set_audio_tokenizer(codec, 32)
+
+    def launches():
+        v = ctypes.c_int64(0)
+        _lib.check(_lib.lib().mimi_debug_read(codec._h, b"launches", ctypes.byref(v), 8, None))
+        return v.value
+
+    def codes_only():
+        t = time.perf_counter()
+        codes = generate_queue(model, prompts, slots=SLOTS, max_audio_frames=caps, decode=False)
+        return time.perf_counter() - t, codes, ""
+
+    def decode_after():
+        t = time.perf_counter()
+        codes, pcm = generate_queue(model, prompts, slots=SLOTS, max_audio_frames=caps, with_codes=True)
+        dt = time.perf_counter() - t
+        assert [len(p) for p in pcm] == [1920 * c for c in caps]
+        return dt, codes, ""
+
+    def streamed(chunk):
+        batch = SlotBatch(model, SLOTS, sampler=Sampler(0.0, 0), chunk=chunk)
+        eng, joined_at, slot_t = batch._eng, {}, {}
+        restart, prefill = eng.restart, eng.prefill
+
+        def timed_restart(b, seed):
+            slot_t[b] = time.perf_counter()
+            restart(b, seed)
+
+        def timed_prefill(items):
+            for b, _, _ in items:
+                joined_at[batch._active[b].ticket] = slot_t[b]
+            prefill(items)
+        eng.restart, eng.prefill = timed_restart, timed_prefill
+        l0, decodes = launches(), [0]
+        dec = codec.decode_slots
+
+        def counted(*a, **k):
+            decodes[0] += 1
+            return dec(*a, **k)
+        codec.decode_slots = counted
+        t = time.perf_counter()
+        tickets = [batch.submit(*prompts[i], caps[i], 0) for i in range(N)]
+        first, last, got, codes = {}, {}, {}, {}
+        for ev in batch.stream():
+            now = time.perf_counter()
+            if len(ev.pcm) and ev.ticket not in first:
+                first[ev.ticket] = now - joined_at[ev.ticket]
+            got[ev.ticket] = got.get(ev.ticket, 0) + len(ev.pcm)
+            if ev.final:
+                last[ev.ticket], codes[ev.ticket] = now - joined_at[ev.ticket], ev.codes
+        dt = time.perf_counter() - t
+        del codec.decode_slots
+        assert [got[t_] for t_ in tickets] == [1920 * c for c in caps]
+        f = np.array([first[t_] for t_ in tickets]) * 1e3
+        e = np.array([last[t_] for t_ in tickets]) * 1e3
+        note = (f"join->first PCM ms median {np.median(f):7.1f} p95 {np.percentile(f, 95):7.1f}  (join->end median "
+                f"{np.median(e):7.1f} p95 {np.percentile(e, 95):7.1f})  codec launches/chunk "
+                f"{(launches() - l0) / max(decodes[0], 1):6.1f} over {decodes[0]} chunks")
+        return dt, [codes[t_] for t_ in tickets], note
+
+    generate_queue(model, prompts[:SLOTS], slots=SLOTS, max_audio_frames=[4] * SLOTS, decode=True)   # warm-up
+    for c in (1, 2, 4, 8):
+        b = SlotBatch(model, SLOTS, sampler=Sampler(0.0, 0), chunk=c)
+        for i in range(SLOTS):
+            b.submit(*prompts[i], 2 * c, 0)
+        list(b.stream())
+    ref = None
+    cases = [("(a) queue decode=False", codes_only), ("(b) queue decode=True", decode_after)]
+    cases += [(f"(c) stream chunk={c}", lambda c=c: streamed(c)) for c in (1, 2, 4, 8)]
+    for r in range(repeats):                       # alternating: every case once per round
+        for name, fn in cases:
+            dt, codes, note = fn()
+            if ref is None:
+                ref = codes
+            same = all(np.array_equal(a, b) for a, b in zip(codes, ref))
+            print(f"{name:24s} run {r}: {useful / dt:8.1f} useful frames/s  {dt:6.3f} s  codes equal to (a)'s: {same}  "
+                  f"{note}", flush=True)
+
+
+if STREAM:
+    stream_bench()
+    sys.exit(0)
 
 generate_queue(model, prompts[:SLOTS], slots=SLOTS, max_audio_frames=[4] * SLOTS, decode=False)   # warm-up: graphs, tables
 generate_batch(model, prompts[:SLOTS], 4 * 80, decode=False)
