@@ -55,11 +55,12 @@ struct GemvParams {
   int xtab_q4_rows;     // int4 weights: total rows of the (quantized) gathered table
   float* x_copy;        // if set: block 0 also stores the raw (un-normed) x rows here [M][K]
   float* qkv_tab;       // EPI_QKV table build: rows [M][(Hq + 2 Hkv) hd] instead of q / KV cache
-  // MFMA path split-K (set by launch_gemm_mfma from ws): slice partials [ksplit][M][N], sum-of-squares [ksplit][M]
+  // MFMA path split-K (set by launch_gemm_mfma / launch_gemm_xs from ws)
   GemmWs* ws;            // the calling engine's scratch (host pointer; required for split launches)
   unsigned lab_launch;   // lab builds of gemm_xs (XS_STAMPS): launch index for the phase stamps
   const void* Wt;        // the weight's fragment-tiled copy (looked up in ws->tiled by launch_gemm_mfma)
-  float* kpart;          // [tile][m chunk][slice][slab] split-K slice partials (+ sum x^2), written sc1
+  float* kpart;          // [tile][m chunk][slice][slab] split-K slice partials, written sc1; a gemm_wide slab ends with
+                         // the rows' sums of squares, a gemm_xs slab ([tile][slice][slab]) has no such tail
   unsigned* kticket;     // [tile][m chunk] arrival tickets (zero between launches)
   int ksplit;
   int no_mfma;           // keep the GEMV's per-row arithmetic at any M (folded-table builds)

@@ -11,10 +11,12 @@
 //                  the next decoder input gather (embed_audio, models.py:79-80)
 //   advance        EOS flag (generation.py:151), code history, frame counter
 // Weights are streamed straight to VGPRs with 16-B loads (GEMV / M <= 16 regime: no LDS
-// round trip); x rows are tiny and served from L1/L2.
+// round trip); x rows are tiny and served from L1/L2.  The GEMVs' gather prologue and the
+// parts of their tail are gemm_parts.h's, shared with the int4 GEMV and the matrix-core kernels.
 #include "c0_process.h"
 #include "csm_kernels.h"
 #include "engine_util.h"
+#include "gemm_parts.h"
 #include "sampler.h"
 #include "xs.h"
 
@@ -165,19 +167,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvParams p) {
   const WT* W = (const WT*)p.W;
   // x gather mode: resolve each needed row's code from the producer's block partials once
   __shared__ int gcode[512];  // codes of the gathered rows (M <= 512)
-  if (p.xpart) {
-    for (int m = wave; m < p.M; m += 4) {
-      const int bb = p.x_step1 ? (m >> 1) : m;
-      if (p.x_step1 && !(m & 1)) continue;
-      const unsigned long long best = wave_argmax_partials(p.xpart + (size_t)bb * p.xpart_stride, p.xpart_n, lane);
-      if (lane == 0) {
-        const int c = min(max(unpack_argmax(best), 0), p.xV - 1);
-        gcode[m] = c;
-        if (blockIdx.x == 0) p.x_codes[(size_t)bb * p.x_codes_K + p.xcb] = c;
-      }
-    }
-    __syncthreads();
-  }
+  if (p.xpart) gp::gather_codes(p, 0, p.M, gcode, blockIdx.x == 0);
   for (int m0 = 0; m0 < p.M; m0 += MT) {
     float acc[MT][RPT];
     float ss[MT];
@@ -252,50 +242,34 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvParams p) {
     }
     __syncthreads();
     constexpr int WPG = G / 64;  // waves per group
-    constexpr int NPAIR = NG * MT * (RPT / 2);
+    typedef gp::PairMap<NG, MT, RPT> PM;
     unsigned long long akey = 0;
     int arow = -1;
-    if (tid < NPAIR) {
-      const int g = tid / (MT * (RPT / 2));
-      const int rem = tid % (MT * (RPT / 2));
-      const int i = rem / (RPT / 2), rp = (rem % (RPT / 2)) * 2;
-      const int m = m0 + i;
+    if (tid < PM::NPAIR) {
+      const PM t(tid);
+      const int m = m0 + t.i;
       if (m < p.M) {
-        float a = 0.f, b = 0.f, sq = 0.f;
+        float a, b, sq = 0.f;
+        gp::pair_sum<WPG>(red, t.g, t.i, t.rp, a, b);
 #pragma unroll
-        for (int w = 0; w < WPG; ++w) {
-          a += red[g * WPG + w][i][rp];
-          b += red[g * WPG + w][i][rp + 1];
-          sq += red[g * WPG + w][i][RPT];
-        }
+        for (int w = 0; w < WPG; ++w) sq += red[t.g * WPG + w][t.i][RPT];
         if (norm) {
           const float sc = rsqrtf(sq / (float)p.K + p.eps);
           a *= sc;
           b *= sc;
         }
-        gemv_epilogue_pair(p, m, blockIdx.x * RPB + g * RPT + rp, a, b);
+        const int n = blockIdx.x * RPB + t.g * RPT + t.rp;
+        gemv_epilogue_pair(p, m, n, a, b);
         if (p.epi == EPI_ARGMAX) {
-          const int n = blockIdx.x * RPB + g * RPT + rp;
-          unsigned long long key = 0;
-          if (n < p.n_valid) key = pack_argmax(a, n);
-          if (n + 1 < p.n_valid) {
-            const unsigned long long kb = pack_argmax(b, n + 1);
-            key = kb > key ? kb : key;
-          }
-          akey = key;
-          arow = i;
+          akey = gp::pair_key(p, n, a, b);
+          arow = t.i;
         }
       }
     }
     if (p.epi == EPI_ARGMAX && wave == 0) {  // block arg-max per row -> partial slot
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
-        unsigned long long v = (tid < NPAIR && arow == i) ? akey : 0ull;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const unsigned long long w = __shfl_xor(v, o, 64);
-          v = w > v ? w : v;
-        }
+        const unsigned long long v = gp::wave_max_key((tid < PM::NPAIR && arow == i) ? akey : 0ull);
         if (lane == 0 && m0 + i < p.M) p.part[(size_t)(m0 + i) * p.part_stride + blockIdx.x] = v;
       }
     }
@@ -347,19 +321,7 @@ __global__ __launch_bounds__(256) void gemv_xl_kernel(GemvParams p) {
     }
   }
   // (2a) gather mode: resolve the rows' codes from the producer's arg-max partials
-  if (p.xpart) {
-    for (int m = wave; m < p.M; m += 4) {
-      const int bb = p.x_step1 ? (m >> 1) : m;
-      if (p.x_step1 && !(m & 1)) continue;
-      const unsigned long long best = wave_argmax_partials(p.xpart + (size_t)bb * p.xpart_stride, p.xpart_n, lane);
-      if (lane == 0) {
-        const int c = min(max(unpack_argmax(best), 0), p.xV - 1);
-        gcode[m] = c;
-        if (blockIdx.x == 0) p.x_codes[(size_t)bb * p.x_codes_K + p.xcb] = c;
-      }
-    }
-    __syncthreads();
-  }
+  if (p.xpart) gp::gather_codes(p, 0, p.M, gcode, blockIdx.x == 0);
   // (2b) stage x (* norm weight) into LDS; sum(x^2) per row once per block
   float ssp[MT];
 #pragma unroll
@@ -435,50 +397,32 @@ __global__ __launch_bounds__(256) void gemv_xl_kernel(GemvParams p) {
       if (lane == 0) red[wave][i][r] = v;
     }
   __syncthreads();
-  constexpr int WPG = G / 64;
-  constexpr int NPAIR = NG * MT * (RPT / 2);
+  typedef gp::PairMap<NG, MT, RPT> PM;
   unsigned long long akey = 0;
   int arow = -1;
-  if (tid < NPAIR) {
-    const int g = tid / (MT * (RPT / 2));
-    const int rem = tid % (MT * (RPT / 2));
-    const int i = rem / (RPT / 2), rp = (rem % (RPT / 2)) * 2;
-    if (i < p.M) {
-      float a = 0.f, b = 0.f;
-#pragma unroll
-      for (int w = 0; w < WPG; ++w) {
-        a += red[g * WPG + w][i][rp];
-        b += red[g * WPG + w][i][rp + 1];
-      }
+  if (tid < PM::NPAIR) {
+    const PM t(tid);
+    if (t.i < p.M) {
+      float a, b;
+      gp::pair_sum<G / 64>(red, t.g, t.i, t.rp, a, b);
       if (norm) {
-        const float sq = (rss[0][i] + rss[1][i]) + (rss[2][i] + rss[3][i]);
+        const float sq = (rss[0][t.i] + rss[1][t.i]) + (rss[2][t.i] + rss[3][t.i]);
         const float sc = rsqrtf(sq / (float)p.K + p.eps);
         a *= sc;
         b *= sc;
       }
-      const int n = blockIdx.x * RPB + g * RPT + rp;
-      gemv_epilogue_pair(p, i, n, a, b);
+      const int n = blockIdx.x * RPB + t.g * RPT + t.rp;
+      gemv_epilogue_pair(p, t.i, n, a, b);
       if (p.epi == EPI_ARGMAX) {
-        unsigned long long key = 0;
-        if (n < p.n_valid) key = pack_argmax(a, n);
-        if (n + 1 < p.n_valid) {
-          const unsigned long long kb = pack_argmax(b, n + 1);
-          key = kb > key ? kb : key;
-        }
-        akey = key;
-        arow = i;
+        akey = gp::pair_key(p, n, a, b);
+        arow = t.i;
       }
     }
   }
   if (p.epi == EPI_ARGMAX && wave == 0) {  // block arg-max per row -> partial slot
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
-      unsigned long long v = (tid < NPAIR && arow == i) ? akey : 0ull;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-      }
+      const unsigned long long v = gp::wave_max_key((tid < PM::NPAIR && arow == i) ? akey : 0ull);
       if (lane == 0 && i < p.M) p.part[(size_t)i * p.part_stride + blockIdx.x] = v;
     }
   }
@@ -589,8 +533,8 @@ __device__ __forceinline__ void attn_block(const AttnParams& p, int m, int kvh, 
   if (p.g_tab) {  // decoder layer 0, steps >= 2: gather this row's QKV from the layer-0 table
     __shared__ int gcode;
     if (wave == 0) {
-      const unsigned long long best = wave_argmax_partials(p.g_part + (size_t)b * p.g_part_stride, p.g_part_n, lane);
-      if (lane == 0) gcode = min(max(unpack_argmax(best), 0), p.g_V - 1);
+      const int c = gp::argmax_code(p.g_part + (size_t)b * p.g_part_stride, p.g_part_n, lane, p.g_V);
+      if (lane == 0) gcode = c;
     }
     __syncthreads();
     const int c = gcode;
@@ -709,8 +653,7 @@ __device__ __forceinline__ void attn_short_head(const AttnParams& p, int m, int 
   }
   const float* qrow = p.q + (size_t)m * p.qs;
   if (gath) {
-    const unsigned long long best = wave_argmax_partials(p.g_part + (size_t)b * p.g_part_stride, p.g_part_n, lane);
-    const int c = min(max(unpack_argmax(best), 0), p.g_V - 1);
+    const int c = gp::argmax_code(p.g_part + (size_t)b * p.g_part_stride, p.g_part_n, lane, p.g_V);
     if (code_out) *code_out = c;
     const float* trow = p.g_tab + (size_t)c * p.g_row;
     qrow = trow;
@@ -1279,8 +1222,8 @@ __global__ void advance_kernel(AdvanceParams p) {
   if (p.last_part) {  // greedy: arg-max of the last head's block partials -> codes[b][K-1]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int b = wave; b < p.B; b += blockDim.x / 64) {
-      const unsigned long long best = wave_argmax_partials(p.last_part + (size_t)b * p.last_stride, p.last_n, lane);
-      if (lane == 0) p.codes[(size_t)b * p.K + p.K - 1] = min(max(unpack_argmax(best), 0), p.V - 1);
+      const int c = gp::argmax_code(p.last_part + (size_t)b * p.last_stride, p.last_n, lane, p.V);
+      if (lane == 0) p.codes[(size_t)b * p.K + p.K - 1] = c;
     }
     __syncthreads();
   }

@@ -30,24 +30,24 @@
 // every partial back with 16-B sc1 loads (MI355X_MICROARCH.md hand-off table, single-counter row),
 // sums them in slice order (deterministic) and runs the epilogue -- RoPE + KV append, residual
 // add, SiLU*up or the heads' arg-max partials -- no second launch.  The slabs and tickets belong
-// to the calling engine (GemmWs), sized outside graph capture by gemm_reserve.
+// to the calling engine (GemmWs), sized outside graph capture by gemm_reserve.  The launcher's
+// tiled-copy lookup, scratch check and reserve are gemm_parts.h's, shared with gemm_xs.hip (the hand-off
+// itself stays written here: folded with gemm_xs_kernel's it rescheduled this kernel); gather_rows_kernel below resolves its code as the GEMVs' gather prologue does.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
 #include "csm_kernels.h"
+#include "gemm_parts.h"
 #include "xs.h"
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned int gu32;
-typedef __attribute__((address_space(1))) const f32x4_t gcf32x4;
+using gp::bf16x8_t;
+using gp::f32x16_t;
+using gp::f32x4_t;
+using gp::u32x2_t;
+using gp::u32x4_t;
 
 constexpr int GP_KC = 64;  // K per stage (= Q4_GROUP)
-constexpr int GK_MAX_SLICES = 16;
 static_assert(GP_KC == Q4_GROUP, "one int4 group per stage");
 
 
@@ -83,9 +83,6 @@ __device__ __forceinline__ float row16_sum(float v) {
 // Split-K combine (the last slice of a tile to arrive): every slice's partial is read with 16-B sc1
 // buffer loads, KS * U of them in flight per thread before the first add, and summed in slice order
 // (deterministic).
-constexpr int GP_RSRC3 = 0x00020000;  // buffer descriptor word 3 (raw 32-bit format)
-constexpr int GP_SC1 = 16;            // cache policy: sc1 (agent-coherent, as __hip_atomic_load/store)
-constexpr int GP_NT = 2;              // cache policy: non-temporal
 template <int KS, int NB, int NBR, int NTH>
 __device__ __forceinline__ void gp_combine(__amdgpu_buffer_rsrc_t rs, float (*ct)[NBR + 1], float* ssb,
                                            int mrows, bool norm, int slab_f, int tid) {
@@ -97,7 +94,7 @@ __device__ __forceinline__ void gp_combine(__amdgpu_buffer_rsrc_t rs, float (*ct
     for (int u = 0; u < U; ++u) {
       const int q = min(q0 + NTH * u, nq - 1);
 #pragma unroll
-      for (int s = 0; s < KS; ++s) v[u][s] = __builtin_amdgcn_raw_buffer_load_b128(rs, q * 16, s * slab_f * 4, GP_SC1);
+      for (int s = 0; s < KS; ++s) v[u][s] = __builtin_amdgcn_raw_buffer_load_b128(rs, q * 16, s * slab_f * 4, gp::SC1);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -118,7 +115,7 @@ __device__ __forceinline__ void gp_combine(__amdgpu_buffer_rsrc_t rs, float (*ct
     float v[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s)
-      v[s] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (NB * NBR + tid) * 4, s * slab_f * 4, GP_SC1));
+      v[s] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (NB * NBR + tid) * 4, s * slab_f * 4, gp::SC1));
     float sum = v[0];
 #pragma unroll
     for (int s = 1; s < KS; ++s) sum += v[s];
@@ -188,7 +185,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_wide_kernel(GemvParams p) {
   const int rt0 = (wave % NGRP) * RTW;
   // this lane's weight bytes in the fragment-tiled copy (gemm_retile): row tile T, stage kst at
   // T * nks + kst blocks of 4 KB (bf16; + 1 KB per step) or 1 KB (int4; scale|bias words after)
-  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.Wt), 0, 0x7fffffff, GP_RSRC3);
+  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.Wt), 0, 0x7fffffff, gp::RSRC3);
   const int nks = p.K / GP_KC, nt32 = (p.N + 31) / 32;
   int wv[RTW], sv[RTW];
 #pragma unroll
@@ -216,9 +213,9 @@ __global__ __launch_bounds__(64 * NW) void gemm_wide_kernel(GemvParams p) {
   // (out of range: zeros, no memory traffic).  Activations first: a wait for the next stage's
   // activations (its LDS store) then leaves every younger weight load of the ring in flight
   // (vmcnt retires in issue order).
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, 0x7fffffff, GP_RSRC3);
-  const __amdgpu_buffer_rsrc_t nrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(nwp), 0, 0x7fffffff, GP_RSRC3);
-  const __amdgpu_buffer_rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.Wt), 0, 0, GP_RSRC3);
+  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, 0x7fffffff, gp::RSRC3);
+  const __amdgpu_buffer_rsrc_t nrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(nwp), 0, 0x7fffffff, gp::RSRC3);
+  const __amdgpu_buffer_rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.Wt), 0, 0, gp::RSRC3);
   int xv[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) xv[i] = (min(m0 + x_c + RPT * i, p.M - 1) * p.xs + x_k4) * 4;
@@ -232,11 +229,11 @@ __global__ __launch_bounds__(64 * NW) void gemm_wide_kernel(GemvParams p) {
 #pragma unroll
     for (int i = 0; i < RTW; ++i) {
       if constexpr (Q4) {
-        g.w[i][0] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv[i], (kc / GP_KC) * 1024, NT ? GP_NT : 0);
+        g.w[i][0] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv[i], (kc / GP_KC) * 1024, NT ? gp::NT : 0);
         g.sb[i] = __builtin_amdgcn_raw_buffer_load_b32(wr, sv[i], (kc / GP_KC) * 128, 0);
       } else {
 #pragma unroll
-        for (int s = 0; s < NS; ++s) g.w[i][s] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv[i], (kc / GP_KC) * 4096 + 1024 * s, NT ? GP_NT : 0);
+        for (int s = 0; s < NS; ++s) g.w[i][s] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv[i], (kc / GP_KC) * 4096 + 1024 * s, NT ? gp::NT : 0);
       }
     }
   };
@@ -403,18 +400,18 @@ __global__ __launch_bounds__(64 * NW) void gemm_wide_kernel(GemvParams p) {
     // slice partial = [NB][NBR] tile values, then [NB] sums of squares; 16-B write-through stores
     const int slab_f = NB * NBR + NB;
     float* slab = p.kpart + ((size_t)(tile * nchunks + mc) * p.ksplit) * slab_f;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(slab, 0, p.ksplit * slab_f * 4, GP_RSRC3);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(slab, 0, p.ksplit * slab_f * 4, gp::RSRC3);
     const int mine = blockIdx.y * slab_f * 4;
     for (int q = tid; q < mrows * (NBR / 4); q += NTH) {
       const int ml = q / (NBR / 4), j = (q % (NBR / 4)) * 4;
       const f32x4_t v = {ct[ml][j], ct[ml][j + 1], ct[ml][j + 2], ct[ml][j + 3]};
-      __builtin_amdgcn_raw_buffer_store_b128(v, rs, q * 16, mine, GP_SC1);
+      __builtin_amdgcn_raw_buffer_store_b128(v, rs, q * 16, mine, gp::SC1);
     }
-    if (norm && tid < mrows) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ssb[tid]), rs, (NB * NBR + tid) * 4, mine, GP_SC1);
+    if (norm && tid < mrows) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ssb[tid]), rs, (NB * NBR + tid) * 4, mine, gp::SC1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {
-      gu32* tk = (gu32*)p.kticket + tile * nchunks + mc;
+      gp::gu32* tk = (gp::gu32*)p.kticket + tile * nchunks + mc;
       const unsigned old = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       last = (old == (unsigned)p.ksplit - 1);
       if (last) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
@@ -494,7 +491,7 @@ static int gemm_ksplit(int N, int K, int M, bool q4) {
   const bool prefill = q4 && M >= 256;
   const int target = (half || prefill) ? 128 : 256;
   int ks = 1;
-  while (tiles * chunks * ks < target && ks < GK_MAX_SLICES && K % (GP_KC * ks * 2) == 0) ks *= 2;
+  while (tiles * chunks * ks < target && ks < gp::MAX_SLICES && K % (GP_KC * ks * 2) == 0) ks *= 2;
   return ks;
 }
 
@@ -524,26 +521,13 @@ static bool gemm_w8(int M) { return M >= GEMM_W8_MIN_M; }
 void launch_gemm_mfma(const GemvParams& p0, int wdt, bool nt, hipStream_t st) {
   GemvParams p = p0;
   const bool q4 = wdt == WDT_Q4;
-  p.Wt = nullptr;
-  if (p.ws) {
-    const auto ti = p.ws->tiled.find(p.W);
-    if (ti != p.ws->tiled.end()) p.Wt = ti->second;
-  }
-  if (!p.Wt) {  // built by the engine (launch_gemm_retile) outside graph capture
-    fprintf(stderr, "csm: no fragment-tiled copy of an N=%d K=%d weight for the MFMA path\n", p.N, p.K);
-    abort();
-  }
+  p.Wt = gp::tiled_copy_or_abort(p);
   const int ks = gemm_ksplit(p.N, p.K, p.M, q4);
   p.ksplit = ks;
   if (ks > 1) {
     size_t tk = 0;
     const size_t need = gemm_need(p.N, p.K, p.M, q4, tk);
-    if (!p.ws || need > p.ws->bytes || tk > p.ws->n) {  // reserved by gemm_reserve outside graph capture
-      fprintf(stderr, "csm: split-K scratch not reserved for N=%d K=%d M=%d\n", p.N, p.K, p.M);
-      abort();
-    }
-    p.kpart = p.ws->kpart;
-    p.kticket = p.ws->tickets;
+    gp::require_scratch(p, need, tk, "");  // reserved by gemm_reserve
   }
   // batch chunks of 64 (MT 2) or one chunk of 32 (MT 1) on grid.z
   const int MT = p.M > 32 ? 2 : 1, nbr = gemm_nbr(p.N, p.K, p.M, q4);
@@ -621,24 +605,7 @@ bool gemm_reserve(GemmWs& ws, int N, int K, int Mmax) {
       tk = std::max(tk, t);
     }
   }
-  bool moved = false;
-  if (slab > ws.bytes) {
-    if (ws.kpart) (void)hipFree(ws.kpart);
-    ws.kpart = nullptr;
-    ws.bytes = 0;
-    if (hipMalloc(&ws.kpart, slab) == hipSuccess) ws.bytes = slab;
-    moved = true;
-  }
-  if (tk > ws.n) {
-    if (ws.tickets) (void)hipFree(ws.tickets);
-    ws.tickets = nullptr;
-    ws.n = 0;
-    if (hipMalloc(&ws.tickets, tk * 4) == hipSuccess && hipMemset(ws.tickets, 0, tk * 4) == hipSuccess &&
-        hipDeviceSynchronize() == hipSuccess)  // (null-stream fill, drained before engine-stream use)
-      ws.n = tk;
-    moved = true;
-  }
-  return moved;
+  return gp::gemm_ws_grow(ws, slab, tk);
 }
 
 void gemm_ws_free(GemmWs& ws) {
@@ -656,23 +623,17 @@ template <typename WT>
 __global__ __launch_bounds__(256) void gather_rows_kernel(GemvParams p) {
   __shared__ int code;
   const int m = blockIdx.x;
-  const int bb = p.x_step1 ? (m >> 1) : m;
   const bool dense = p.x_step1 && !(m & 1);
   if (!dense && threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    const unsigned long long best = wave_argmax_partials(p.xpart + (size_t)bb * p.xpart_stride, p.xpart_n, lane);
-    if (lane == 0) {
-      const int c = min(max(unpack_argmax(best), 0), p.xV - 1);
-      code = c;
-      p.x_codes[(size_t)bb * p.x_codes_K + p.xcb] = c;
-    }
+    const int c = gp::resolve_code(p, m, threadIdx.x, true);
+    if (threadIdx.x == 0) code = c;
   }
   __syncthreads();
   float* out = p.out + (size_t)m * p.os;
   const size_t trow = dense ? 0 : (size_t)code + (size_t)p.xV * p.xcb;
   for (int k = threadIdx.x * 8; k < p.K; k += 256 * 8) {
     float v[8];
-    if (dense) W8<float>::load(p.x + (size_t)bb * p.xs + k, v);
+    if (dense) W8<float>::load(p.x + (size_t)gp::dense_row(p, m) * p.xs + k, v);
     else if (p.xtab_f32) W8<float>::load((const float*)p.xtab + trow * p.K + k, v);
     else if (p.xtab_q4_rows) q4_load8((const uint8_t*)p.xtab, (size_t)p.xtab_q4_rows, p.K, trow, k, v);
     else W8<WT>::load((const WT*)p.xtab + trow * p.K + k, v);

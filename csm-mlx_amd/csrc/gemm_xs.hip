@@ -18,7 +18,8 @@
 // activation parts are exact, products exact in fp32, fp32 accumulation; the RMSNorm row scale is
 // applied after the dot product (the producer multiplied the norm weight in before splitting).
 // Split-K slices publish write-through (sc1) partial tiles and take an arrival ticket; the last
-// slice of a tile sums them in slice order and runs the epilogue (deterministic).
+// slice of a tile sums them in slice order and runs the epilogue (deterministic).  The
+// launcher's tiled-copy lookup, scratch check and reserve are gemm_parts.h's, shared with gemm_kernels.hip.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -26,24 +27,22 @@
 #include "../../include/csm_hip.h"
 #include "../../include/csm_hip_prof.h"
 #include "csm_kernels.h"
+#include "gemm_parts.h"
 #include "xs.h"
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned int gu32;
+using gp::bf16x8_t;
+using gp::f32x16_t;
+using gp::f32x4_t;
+using gp::u32x4_t;
+using gp::MAX_SLICES;
 
 constexpr int XK = 64;                 // K per stage
 constexpr int XW_MAX = 4;              // waves per block: 2, or 4 where the grid would leave SIMDs idle
-constexpr int RSRC3 = 0x00020000;      // buffer descriptor word 3 (raw 32-bit format)
-constexpr int SC1 = 16;                // cache policy: sc1 (agent-coherent)
-constexpr int MAX_SLICES = 16;
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, RSRC3);
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, gp::RSRC3);
 }
 
 // Q4: int4 weights (MLX affine, group 64 = one stage) from the fragment-tiled int4 copy: the nibbles
@@ -66,7 +65,7 @@ __device__ __forceinline__ void combine(__amdgpu_buffer_rsrc_t rs, float (*ct)[N
     for (int u = 0; u < UB; ++u) {
       const int q = min(tid + NTH * (u0 + u), nq - 1);
 #pragma unroll
-      for (int s = 0; s < KS; ++s) v[u][s] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, q * 16, s * slab_f * 4, SC1));
+      for (int s = 0; s < KS; ++s) v[u][s] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, q * 16, s * slab_f * 4, gp::SC1));
     }
 #pragma unroll
     for (int u = 0; u < UB; ++u) {
@@ -376,13 +375,13 @@ __global__ __launch_bounds__(64 * XW) void gemm_xs_kernel(GemvParams p) {
     for (int q = tid; q < mrows * (NBR / 4); q += NTH) {
       const int ml = q / (NBR / 4), j = (q % (NBR / 4)) * 4;
       const f32x4_t v = {ct[ml][j], ct[ml][j + 1], ct[ml][j + 2], ct[ml][j + 3]};
-      __builtin_amdgcn_raw_buffer_store_b128(v, rs, q * 16, mine, SC1);
+      __builtin_amdgcn_raw_buffer_store_b128(v, rs, q * 16, mine, gp::SC1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     XS_STAMP(4);
     if (tid == 0) {
-      gu32* tk = (gu32*)p.kticket + tile;
+      gp::gu32* tk = (gp::gu32*)p.kticket + tile;
       const unsigned old = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       last = (old == (unsigned)ks - 1);
       if (last) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
@@ -623,37 +622,16 @@ bool gemm_xs_reserve(GemmWs& ws, int N, int K, int Mmax) {
       slab = std::max(slab, xs_need(N, K, m, h == 1, t));
       tk = std::max(tk, t);
     }
-  bool moved = false;
-  if (slab > ws.bytes) {
-    if (ws.kpart) (void)hipFree(ws.kpart);
-    ws.kpart = nullptr;
-    ws.bytes = 0;
-    if (hipMalloc(&ws.kpart, slab) == hipSuccess) ws.bytes = slab;
-    moved = true;
-  }
-  if (tk > ws.n) {
-    if (ws.tickets) (void)hipFree(ws.tickets);
-    ws.tickets = nullptr;
-    ws.n = 0;
-    if (hipMalloc(&ws.tickets, tk * 4) == hipSuccess && hipMemset(ws.tickets, 0, tk * 4) == hipSuccess &&
-        hipDeviceSynchronize() == hipSuccess)
-      ws.n = tk;
-    moved = true;
-  }
-  return moved;
+  return gp::gemm_ws_grow(ws, slab, tk);
 }
 
 void launch_gemm_xs(const GemvParams& p0, int epi, hipStream_t st, bool nt_w, int wdt) {
   GemvParams p = p0;
   p.epi = epi;
-  p.Wt = nullptr;
-  if (p.ws) {
-    const auto ti = p.ws->tiled.find(p.W);
-    if (ti != p.ws->tiled.end()) p.Wt = ti->second;
-  }
-  if (!p.Wt || !p.xs_in || p.M > GEMM_XS_MAX_M || p.scale || (wdt == WDT_Q4 && !p.hs_in) ||
+  p.Wt = gp::tiled_copy_or_abort(p);
+  if (!p.xs_in || p.M > GEMM_XS_MAX_M || p.scale || (wdt == WDT_Q4 && !p.hs_in) ||
       !gemm_xs_eligible(p.N, p.K, p.M, wdt)) {
-    fprintf(stderr, "csm: gemm_xs launch without a tiled weight / split activations, or with an unsupported option (N=%d K=%d M=%d)\n",
+    fprintf(stderr, "csm: gemm_xs launch without split activations, or with an unsupported option (N=%d K=%d M=%d)\n",
             p.N, p.K, p.M);
     abort();
   }
@@ -668,12 +646,7 @@ void launch_gemm_xs(const GemvParams& p0, int epi, hipStream_t st, bool nt_w, in
   if (ks > 1) {
     size_t tk = 0;
     const size_t need = xs_need(p.N, p.K, p.M, head, tk);
-    if (!p.ws || need > p.ws->bytes || tk > p.ws->n) {  // reserved by gemm_xs_reserve outside graph capture
-      fprintf(stderr, "csm: gemm_xs split-K scratch not reserved for N=%d K=%d M=%d\n", p.N, p.K, p.M);
-      abort();
-    }
-    p.kpart = p.ws->kpart;
-    p.kticket = p.ws->tickets;
+    gp::require_scratch(p, need, tk, "gemm_xs ");  // reserved by gemm_xs_reserve
   }
   // non-temporal weight loads: the audio_head slices and the backbone (read once per frame) stay out of the
   // caches the decoder's weights are re-read from

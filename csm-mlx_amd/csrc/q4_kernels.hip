@@ -5,11 +5,13 @@
 // Reference: nn.quantize(model, group_size=64, bits=4) (run_streaming_csm_mlx.py:811-818,
 // README.md:108-111).  The quantization rule restated here and in oracle/quant_oracle.py is
 // mlx's affine ``quantize`` (un-vendored dependency mlx>=0.22.1, pyproject.toml:13); the layout
-// is common.h's q4 layout.
+// is common.h's q4 layout.  The quantized GEMV's gather prologue and the parts of its tail are
+// gemm_parts.h's, shared with the dense GEMVs.
 #include <climits>
 
 #include "../../include/csm_hip_prof.h"
 #include "csm_kernels.h"
+#include "gemm_parts.h"
 #include "xs.h"
 
 // ============================================================================ quantize
@@ -264,20 +266,7 @@ __global__ __launch_bounds__(256) void gemv_q4_kernel(GemvParams p) {
   for (int m0 = 0; m0 < p.M; m0 += MT) {
     const int mn = min(MT, p.M - m0);
     // (2a) gather mode: codes of the gathered rows from the producer's arg-max partials
-    if (p.xpart) {
-      for (int i = wave; i < mn; i += 4) {
-        const int m = m0 + i;
-        const int bb = p.x_step1 ? (m >> 1) : m;
-        if (p.x_step1 && !(m & 1)) continue;
-        const unsigned long long best = wave_argmax_partials(p.xpart + (size_t)bb * p.xpart_stride, p.xpart_n, lane);
-        if (lane == 0) {
-          const int c = min(max(unpack_argmax(best), 0), p.xV - 1);
-          gcode[i] = c;
-          if (blockIdx.x == 0) p.x_codes[(size_t)bb * p.x_codes_K + p.xcb] = c;
-        }
-      }
-      __syncthreads();
-    }
+    if (p.xpart) gp::gather_codes(p, m0, mn, gcode, blockIdx.x == 0);
     // (2b) stage x * nw, half-group sums, sum(x^2)
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
@@ -404,34 +393,26 @@ __global__ __launch_bounds__(256) void gemv_q4_kernel(GemvParams p) {
     unsigned long long akey[MT];
 #pragma unroll
     for (int i = 0; i < MT; ++i) akey[i] = 0ull;
+    // gemv_epilogue_pair and the shared key (gp::pair_key), behind this kernel's own guard: its last
+    // block may be partial, where the dense GEMVs cover N in whole blocks and have none
     auto emit = [&](int i, int n, float a, float b) {
-      if (n >= p.N) return;  // partial last block
+      if (n >= p.N) return;
       gemv_epilogue_pair(p, m0 + i, n, a, b);
       if (p.epi == EPI_ARGMAX) {
-        unsigned long long key = n < p.n_valid ? pack_argmax(a, n) : 0ull;
-        if (n + 1 < p.n_valid) {
-          const unsigned long long kb = pack_argmax(b, n + 1);
-          key = kb > key ? kb : key;
-        }
+        const unsigned long long key = gp::pair_key(p, n, a, b);
         akey[i] = key > akey[i] ? key : akey[i];
       }
     };
     if constexpr (WPG > 1) {
-      constexpr int NPAIR = NG * MT * (RPT / 2);
-      if (tid < NPAIR) {
-        const int g = tid / (MT * (RPT / 2));
-        const int rem = tid % (MT * (RPT / 2));
-        const int i = rem / (RPT / 2), rp = (rem % (RPT / 2)) * 2;
+      typedef gp::PairMap<NG, MT, RPT> PM;
+      if (tid < PM::NPAIR) {
+        const PM t(tid);
 #pragma unroll
         for (int ii = 0; ii < MT; ++ii) {
-          if (ii == i && i < mn) {
-            float a = 0.f, b = 0.f;
-#pragma unroll
-            for (int w = 0; w < WPG; ++w) {
-              a += red[g * WPG + w][ii][rp];
-              b += red[g * WPG + w][ii][rp + 1];
-            }
-            emit(ii, blockIdx.x * RPB + g * RPT + rp, a * sc[ii], b * sc[ii]);
+          if (ii == t.i && t.i < mn) {
+            float a, b;
+            gp::pair_sum<WPG>(red, t.g, ii, t.rp, a, b);
+            emit(ii, blockIdx.x * RPB + t.g * RPT + t.rp, a * sc[ii], b * sc[ii]);
           }
         }
       }
@@ -445,12 +426,7 @@ __global__ __launch_bounds__(256) void gemv_q4_kernel(GemvParams p) {
     if (p.epi == EPI_ARGMAX) {  // block arg-max per row -> partial slot
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
-        unsigned long long v = akey[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const unsigned long long w = __shfl_xor(v, o, 64);
-          v = w > v ? w : v;
-        }
+        const unsigned long long v = gp::wave_max_key(akey[i]);
         if (lane == 0) bk[wave][i] = v;
       }
       __syncthreads();

@@ -198,6 +198,31 @@ def test_folded_layer0_qkv_table_matches_gemv(tiny, which, dtype):
     del model
 
 
+@pytest.mark.parametrize("dtype", ["float32", "bf16", "q4"])
+def test_unfolded_projection_matches_oracle(tiny, dtype):
+    """fold_proj off: at codebook steps >= 2 the projection GEMV gathers its input row from audio_emb in
+    the weight's own type (float32 / bf16 / int4) instead of reading the folded fp32 table -- the gather
+    branch no other test reaches past step 1.  Greedy codes bit-exact against the oracle."""
+    from csm_mlx import _lib
+    from csm_mlx.generation import generate_codes_batch
+    from csm_mlx.sampling import Sampler
+    from csm_mlx.tokenizers import tokenize_text_segment
+    from oracle.csm_oracle import text_frame
+    args, w = tiny
+    K = args.n_audio_codebooks
+    model = _model(args, w, dtype, max_batch=2)
+    o = oracle_for(args, w, bf16=(dtype == "bf16"), q4=(dtype == "q4"))
+    id_sets = [tiny_prompt_ids(40 + b, 3 + b) for b in range(2)]
+    _lib.check(_lib.lib().csm_set_option(model.engine, b"fold_proj", 0))
+    hist, n, _ = generate_codes_batch(model, [tokenize_text_segment(i, 0, K) for i in id_sets], 12,
+                                      sampler=Sampler(0.0, 0))
+    for b, ids in enumerate(id_sets):
+        ref = o.generate_codes(*text_frame(ids, K), 12)
+        assert n[b] == len(ref)
+        assert first_divergence(hist[: n[b], b], ref) is None, f"utterance {b} diverges"
+    del model
+
+
 def test_eos_first_frame_stops_generation(tiny):
     """generation.py:151-152 / :163-165: an all-zero frame is EOS -- it is not appended, and with no
     samples generate() returns zeros((0,)).  Zeroed heads make every logit 0, so the first-max greedy
