@@ -51,15 +51,13 @@ class _EngineSlots:
     def __init__(self, model: CSM, slots: int, sampler: Sampler, processors):
         self.model = model
         self.cache = FrameCache(model, slots, sampler, np.zeros(slots, np.uint64), processors)
-        self.L = self.cache.L
+        self._call = self.cache._call
 
     def restart(self, b: int, seed: int):
-        self.cache._check()
-        _lib.check(self.L.csm_slot_restart(self.model.engine, b, ctypes.c_uint64(int(seed) & ((1 << 64) - 1))))
+        self._call("csm_slot_restart", b, ctypes.c_uint64(int(seed) & ((1 << 64) - 1)))
 
     def release(self, b: int):
-        self.cache._check()
-        _lib.check(self.L.csm_slot_release(self.model.engine, b))
+        self._call("csm_slot_release", b)
 
     def prefill(self, items: Sequence[Tuple[int, np.ndarray, np.ndarray]]):
         self.cache.prefill_batch(items)
@@ -71,32 +69,28 @@ class _EngineSlots:
 
     def wait(self):
         """Wait for the enqueued frames and check the three hand-off error flags, as ``run`` does."""
-        self.cache._check()
-        _lib.check(self.L.csm_synchronize(self.model.engine))
+        self._call("csm_synchronize")
 
     def ring(self) -> Tuple[int, int, int]:
         """(device pointer of the code history [F_cap][B][K], F_cap, global frames run): frame g of the
         session is ring row g % F_cap."""
-        self.cache._check()
         p = ctypes.c_void_p()
-        _lib.check(self.L.csm_codes_device_ptr(self.model.engine, ctypes.byref(p)))
+        self._call("csm_codes_device_ptr", ctypes.byref(p))
         return int(p.value), int(self.model.max_frames), int(self.cache.frames)
 
     def poll(self) -> Tuple[np.ndarray, np.ndarray]:
         """(n_frames [B], done [B]) of the slots' current utterances."""
-        self.cache._check()
         n = np.zeros(self.cache.B, np.int32)
         d = np.zeros(self.cache.B, np.uint8)
-        _lib.check(self.L.csm_read_codes(self.model.engine, None, _lib.ptr(n), _lib.ptr(d), None))
+        self._call("csm_read_codes", None, _lib.ptr(n), _lib.ptr(d), None)
         return n, d.astype(bool)
 
     def read(self, b: int, cap: int) -> np.ndarray:
         """codes (F, K) int32 of slot b's utterance (EOS excluded)."""
-        self.cache._check()
         out = np.zeros((max(cap, 1), self.model.n_audio_codebooks), np.int32)
         n = ctypes.c_int(0)
         d = ctypes.c_uint8(0)
-        _lib.check(self.L.csm_slot_read(self.model.engine, b, _lib.ptr(out), cap, ctypes.byref(n), ctypes.byref(d)))
+        self._call("csm_slot_read", b, _lib.ptr(out), cap, ctypes.byref(n), ctypes.byref(d))
         return out[: n.value].copy()
 
 
@@ -190,24 +184,38 @@ class SlotBatch:
         if joins:
             self._eng.prefill(joins)
 
+    def _chunk_frames(self) -> int:
+        """The frames of the next chunk: ``chunk``, shortened to the smallest remaining budget among the
+        active slots; 0 when no slot is active (with every slot free, ``_fill`` has emptied the queue)."""
+        left = [j.cap - j.ran for j in self._active if j is not None]
+        return min(self.chunk, min(left)) if left else 0
+
+    def _advance(self, n: int, done) -> Generator[Tuple[int, int, bool, Optional[np.ndarray]], None, None]:
+        """After a chunk of n frames and its poll: (slot, ticket, final, codes) of every active slot in
+        slot order.  ``final``: the utterance reached EOS or its cap -- its slot is read (``codes``, else
+        None) and freed for the next ``_fill``."""
+        for b, job in enumerate(self._active):
+            if job is None:
+                continue
+            job.ran += n
+            final = bool(done[b]) or job.ran >= job.cap
+            codes = None
+            if final:
+                codes = self._eng.read(b, job.cap)
+                self._active[b] = None
+            yield b, job.ticket, final, codes
+
     def run(self) -> Generator[Tuple[int, np.ndarray], None, None]:
         while True:
             yield from self._fill()
-            active = [j for j in self._active if j is not None]
-            if not active:             # (with every slot free, _fill has emptied the queue)
+            n = self._chunk_frames()
+            if not n:
                 return
-            n = min(self.chunk, min(j.cap - j.ran for j in active))
             self._eng.run(n)
             _, done = self._eng.poll()
-            for b, job in enumerate(self._active):
-                if job is None:
-                    continue
-                job.ran += n
-                if done[b] or job.ran >= job.cap:
-                    codes = self._eng.read(b, job.cap)
-                    self._active[b] = None
-                    yield job.ticket, codes
-
+            for _, ticket, final, codes in self._advance(n, done):
+                if final:
+                    yield ticket, codes
 
     def stream(self, codec=None) -> Generator[StreamChunk, None, None]:
         """``run`` with audio: yields ``StreamChunk(ticket, pcm, final, codes)`` as the frames of each
@@ -261,10 +269,9 @@ class SlotBatch:
             for b in self._joined:
                 delivered[b] = 0
             resets = list(self._joined)
-            active = [j for j in self._active if j is not None]
-            if not active:
+            n = self._chunk_frames()
+            if not n:
                 break
-            n = min(self.chunk, min(j.cap - j.ran for j in active))
             ptr, F_cap, g0 = self._eng.ring()
             self._eng.run(n, sync=False)
             if prev is not None:
@@ -272,21 +279,27 @@ class SlotBatch:
             self._eng.wait()
             n_frames, done = self._eng.poll()
             rows = []
-            for b, job in enumerate(self._active):
-                if job is None:
-                    continue
-                job.ran += n
-                final = bool(done[b]) or job.ran >= job.cap
+            for b, ticket, final, codes in self._advance(n, done):
                 valid = max(0, min(n, int(n_frames[b]) - delivered[b]))
                 delivered[b] += valid
-                codes = None
-                if final:
-                    codes = self._eng.read(b, job.cap)
-                    self._active[b] = None
-                rows.append((b, job.ticket, valid, final, codes))
+                rows.append((b, ticket, valid, final, codes))
             prev = {"resets": resets, "rows": rows, "ptr": ptr, "F_cap": F_cap, "first_row": g0 % F_cap, "n": n}
         if prev is not None:
             yield from events(prev)
+
+
+def _queued(model, prompts, max_audio_length_ms, slots, temperature, top_k, sampler, seeds, max_audio_frames,
+            logits_processors, chunk) -> Tuple[SlotBatch, List[int]]:
+    """What both queue entry points begin with: a ``SlotBatch`` with every prompt submitted under its frame
+    cap and seed.  Returns (batch, the tickets in prompt order)."""
+    smp = _resolve_sampler(temperature, sampler, top_k)
+    n = len(prompts)
+    caps = [int(max_audio_length_ms / 80)] * n if max_audio_frames is None else [int(c) for c in max_audio_frames]
+    if len(caps) != n:
+        raise ValueError("need one frame cap per prompt")
+    seed_list = _seed_list(seeds, n)
+    batch = SlotBatch(model, slots, sampler=smp, logits_processors=logits_processors, chunk=chunk)
+    return batch, [batch.submit(t, m, caps[i], int(seed_list[i])) for i, (t, m) in enumerate(prompts)]
 
 
 def generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], max_audio_length_ms: float = 10_000,
@@ -297,18 +310,13 @@ def generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]],
     order (or codes if decode=False; (codes, waveforms) with ``with_codes``).  ``max_audio_frames``: one
     frame cap per prompt (default: ``max_audio_length_ms`` for all).  Seeds follow ``generate_batch``: a
     scalar s gives s + i for prompt i."""
-    smp = _resolve_sampler(temperature, sampler, top_k)
-    n = len(prompts)
-    caps = [int(max_audio_length_ms / 80)] * n if max_audio_frames is None else [int(c) for c in max_audio_frames]
-    if len(caps) != n:
-        raise ValueError("need one frame cap per prompt")
-    seed_list = _seed_list(seeds, n)
-    batch = SlotBatch(model, slots, sampler=smp, logits_processors=logits_processors, chunk=chunk)
-    tickets = [batch.submit(t, m, caps[i], int(seed_list[i])) for i, (t, m) in enumerate(prompts)]
+    batch, tickets = _queued(model, prompts, max_audio_length_ms, slots, temperature, top_k, sampler, seeds,
+                             max_audio_frames, logits_processors, chunk)
     got = dict(batch.run())
     codes = [got[t] for t in tickets]
     if not decode:
         return codes
+    n = len(prompts)
     n_frames = np.array([len(c) for c in codes], np.int32)
     hist = np.zeros((int(n_frames.max()) if n else 0, n, model.n_audio_codebooks), np.int32)
     for i, c in enumerate(codes):
@@ -326,13 +334,8 @@ def stream_generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.nda
     the new (v * 1920,) float32 samples of that prompt's utterance (v >= 0), ``final`` on its last event.  The
     concatenation per prompt is what ``stream_generate`` yields for it alone.  The registered audio tokenizer
     needs ``max_batch >= slots`` and ``max_frames >=`` the largest frame cap."""
-    smp = _resolve_sampler(temperature, sampler, top_k)
-    n = len(prompts)
-    caps = [int(max_audio_length_ms / 80)] * n if max_audio_frames is None else [int(c) for c in max_audio_frames]
-    if len(caps) != n:
-        raise ValueError("need one frame cap per prompt")
-    seed_list = _seed_list(seeds, n)
-    batch = SlotBatch(model, slots, sampler=smp, logits_processors=logits_processors, chunk=chunk)
-    index = {batch.submit(t, m, caps[i], int(seed_list[i])): i for i, (t, m) in enumerate(prompts)}
+    batch, tickets = _queued(model, prompts, max_audio_length_ms, slots, temperature, top_k, sampler, seeds,
+                             max_audio_frames, logits_processors, chunk)
+    index = {t: i for i, t in enumerate(tickets)}
     for ev in batch.stream():
         yield index[ev.ticket], ev.pcm, ev.final

@@ -14,8 +14,10 @@ generation.py:156).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
+import time
 from typing import Any, Callable, Generator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -87,10 +89,10 @@ class FrameCache:
         self.sampler = sampler
         self.seeds = _seed_list(seeds, batch_size)
         self.L = _lib.lib()
-        _lib.check(self.L.csm_begin(model.engine, batch_size, _lib.ptr(self.seeds), sampler.temp, sampler.top_k))
+        self._gen = getattr(model, "_generation", 0)   # the model's current one until this batch has begun
+        self._call("csm_begin", batch_size, _lib.ptr(self.seeds), sampler.temp, sampler.top_k)
         if not sampler.greedy and sampler.filtered:
-            _lib.check(self.L.csm_set_sampler_filters(model.engine, sampler.top_p, sampler.min_p,
-                                                      sampler.min_tokens_to_keep))
+            self._call("csm_set_sampler_filters", sampler.top_p, sampler.min_p, sampler.min_tokens_to_keep)
         if processors is not None:
             bias, pen = processors
             idx = np.asarray(bias.indices if bias else (), np.int64)
@@ -98,10 +100,9 @@ class FrameCache:
             if idx.size and (idx.min() < 0 or idx.max() >= model.n_audio_vocab):   # no silent clamp
                 raise ValueError(f"logit_bias index outside [0, {model.n_audio_vocab}): {idx.min()} .. {idx.max()}")
             idx = np.ascontiguousarray(idx, np.int32)
-            _lib.check(self.L.csm_set_c0_processors(model.engine, len(idx), _lib.ptr(idx), _lib.ptr(val),
-                                                    pen.penalty if pen else 0.0, pen.context_size if pen else 0))
-        model._generation = getattr(model, "_generation", 0) + 1
-        self._gen = model._generation
+            self._call("csm_set_c0_processors", len(idx), _lib.ptr(idx), _lib.ptr(val),
+                       pen.penalty if pen else 0.0, pen.context_size if pen else 0)
+        model._generation = self._gen = self._gen + 1
         self.frames = 0
 
     def _check(self):
@@ -109,31 +110,32 @@ class FrameCache:
             raise RuntimeError("this FrameCache was superseded: a newer generation started on the same model "
                                "(the engine holds one active generation per model)")
 
-    def prefill(self, b: int, tokens: np.ndarray, mask: np.ndarray):
+    def _call(self, name: str, *args):
+        """Every engine call of this cache: ``name(engine, *args)``, refused once the cache is superseded."""
         self._check()
+        _lib.check(getattr(self.L, name)(self.model.engine, *args))
+
+    def prefill(self, b: int, tokens: np.ndarray, mask: np.ndarray):
         t = np.ascontiguousarray(tokens, np.int32)
         m = np.ascontiguousarray(mask, np.uint8)
-        _lib.check(self.L.csm_prefill(self.model.engine, b, t.shape[0], _lib.ptr(t), _lib.ptr(m)))
+        self._call("csm_prefill", b, t.shape[0], _lib.ptr(t), _lib.ptr(m))
 
     def prefill_batch(self, items: Sequence[Tuple[int, np.ndarray, np.ndarray]]):
         """prefill for several utterances in one pass per <= max_seq_len rows (csm_prefill_batch):
         items = (b, tokens, mask) with distinct b."""
-        self._check()
         if not items:
-            return
+            return self._check()
         utts = np.array([b for b, _, _ in items], np.int32)
         Ts = np.array([t.shape[0] for _, t, _ in items], np.int32)
         toks = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int32) for _, t, _ in items]), np.int32)
         msks = np.ascontiguousarray(np.concatenate([np.asarray(m, np.uint8) for _, _, m in items]), np.uint8)
-        _lib.check(self.L.csm_prefill_batch(self.model.engine, len(items), _lib.ptr(utts), _lib.ptr(Ts),
-                                            _lib.ptr(toks), _lib.ptr(msks)))
+        self._call("csm_prefill_batch", len(items), _lib.ptr(utts), _lib.ptr(Ts), _lib.ptr(toks), _lib.ptr(msks))
 
     def run(self, nframes: int, sync: bool = True) -> bool:
         """Enqueue nframes frame graphs; with sync, wait and return whether every utterance is done
         (without, return False at once: the caller polls ``done()``, which waits for the frames)."""
-        self._check()
         done = ctypes.c_int(0)
-        _lib.check(self.L.csm_run_frames(self.model.engine, nframes, ctypes.byref(done) if sync else None))
+        self._call("csm_run_frames", nframes, ctypes.byref(done) if sync else None)
         self.frames += nframes
         return bool(done.value)
 
@@ -141,26 +143,30 @@ class FrameCache:
         """Enqueue nframes frames and return whether every utterance had hit EOS by the end of the
         PREVIOUS chunk run this way (None for the first): the EOS poll one chunk behind, so the GPU never
         waits on the host (csm_run_frames_ahead)."""
-        self._check()
         prev = ctypes.c_int(-1)
-        _lib.check(self.L.csm_run_frames_ahead(self.model.engine, nframes, ctypes.byref(prev)))
+        self._call("csm_run_frames_ahead", nframes, ctypes.byref(prev))
         self.frames += nframes
         return None if prev.value < 0 else bool(prev.value)
 
-    def run_processed(self, processors: Sequence[Callable], c0_history: Optional[list]) -> bool:
-        """One frame with host ``logits_processors`` applied to the c0 logits (generation.py:42-61):
-        the engine stops after codebook0_head, each processor maps (stack(c0_history) or zeros((0,)),
-        logits (B, V)) -> logits, and the frame finishes on the GPU from the processed logits.
-        Appends this frame's c0 (B, 1) to ``c0_history``; returns whether every utterance is done."""
-        self._check()
+    def _c0_logits(self, processors: Sequence[Callable], c0_history: Optional[list]) -> np.ndarray:
+        """The frame up to codebook0_head (csm_frame_c0_logits), then each processor maps
+        (stack(c0_history) or zeros((0,)), logits (B, V)) -> logits (generation.py:42-49)."""
         V = self.model.n_audio_vocab
         logits = np.zeros((self.B, V), np.float32)
-        _lib.check(self.L.csm_frame_c0_logits(self.model.engine, _lib.ptr(logits)))
+        self._call("csm_frame_c0_logits", _lib.ptr(logits))
         hist = np.stack(c0_history, 0) if c0_history else np.zeros((0,), np.int32)
         for proc in processors:
             logits = np.ascontiguousarray(np.asarray(proc(hist, logits), np.float32).reshape(self.B, V))
+        return logits
+
+    def run_processed(self, processors: Sequence[Callable], c0_history: Optional[list]) -> bool:
+        """One frame with host ``logits_processors`` applied to the c0 logits (generation.py:42-61):
+        the engine stops after codebook0_head for them (``_c0_logits``), and the frame finishes on the GPU
+        from the processed logits.
+        Appends this frame's c0 (B, 1) to ``c0_history``; returns whether every utterance is done."""
+        logits = self._c0_logits(processors, c0_history)
         done = ctypes.c_int(0)
-        _lib.check(self.L.csm_frame_finish(self.model.engine, _lib.ptr(logits), ctypes.byref(done)))
+        self._call("csm_frame_finish", _lib.ptr(logits), ctypes.byref(done))
         self.frames += 1
         if c0_history is not None:
             c0_history.append(self.last_codes()[:, :1].copy())
@@ -172,13 +178,8 @@ class FrameCache:
         applied per codebook): c0 logits -> processors -> sampler -> csm_frame_host_step, which feeds
         the codes forward and returns the next codebook's logits, K times.  Returns whether every
         utterance is done."""
-        self._check()
         V, K = self.model.n_audio_vocab, self.model.n_audio_codebooks
-        logits = np.zeros((self.B, V), np.float32)
-        _lib.check(self.L.csm_frame_c0_logits(self.model.engine, _lib.ptr(logits)))
-        hist = np.stack(c0_history, 0) if c0_history else np.zeros((0,), np.int32)
-        for proc in processors:
-            logits = np.ascontiguousarray(np.asarray(proc(hist, logits), np.float32).reshape(self.B, V))
+        logits = self._c0_logits(processors, c0_history)
         done = ctypes.c_int(0)
         for i in range(K):
             raw = np.asarray(sampler(logits)).reshape(self.B)
@@ -188,39 +189,55 @@ class FrameCache:
             if i == 0 and c0_history is not None:
                 c0_history.append(codes[:, None].copy())
             out = np.zeros((self.B, V), np.float32)
-            _lib.check(self.L.csm_frame_host_step(self.model.engine, _lib.ptr(codes),
-                                                  _lib.ptr(out) if i + 1 < K else None, ctypes.byref(done)))
+            self._call("csm_frame_host_step", _lib.ptr(codes), _lib.ptr(out) if i + 1 < K else None,
+                       ctypes.byref(done))
             logits = out
         self.frames += 1
         return bool(done.value)
 
+    def step(self, processors: Optional[Sequence[Callable]] = None, c0_history: Optional[list] = None) -> bool:
+        """One frame the way this cache needs it: every code from the host with a ``HostSampler``, paused
+        after codebook0_head for host ``processors``, else the plain graph.  Appends this frame's c0 (B, 1)
+        to ``c0_history`` when one is given; returns whether every utterance is done."""
+        if isinstance(self.sampler, HostSampler):
+            return self.run_host_sampled(self.sampler, processors or (), c0_history)
+        if processors:
+            return self.run_processed(processors, c0_history)
+        done = self.run(1)
+        if c0_history is not None:
+            c0_history.append(self.last_codes()[:, :1].copy())
+        return done
+
+    def forced(self, codes: np.ndarray, c0=None, ci=None, ce=None):
+        """One teacher-forced frame (csm_frame_forced): the given codes (B, K) are fed forward in place of
+        the sampled ones.  Fills the float32 arrays that are passed: the logits c0 (B, V) and ci (K-1, B, V),
+        the cross entropy of every forced code ce (B, K), reduced on the GPU."""
+        codes = np.ascontiguousarray(codes, np.int32)
+        self._call("csm_frame_forced", _lib.ptr(codes), *(None if a is None else _lib.ptr(a) for a in (c0, ci, ce)))
+
     def codes(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(history [F,B,K], n_frames [B], done [B])."""
-        self._check()
         F = ctypes.c_int(0)
-        _lib.check(self.L.csm_read_codes(self.model.engine, None, None, None, ctypes.byref(F)))
+        self._call("csm_read_codes", None, None, None, ctypes.byref(F))
         hist = np.zeros((F.value, self.B, self.model.n_audio_codebooks), np.int32)
         n = np.zeros(self.B, np.int32)
         d = np.zeros(self.B, np.uint8)
-        _lib.check(self.L.csm_read_codes(self.model.engine, _lib.ptr(hist), _lib.ptr(n), _lib.ptr(d), None))
+        self._call("csm_read_codes", _lib.ptr(hist), _lib.ptr(n), _lib.ptr(d), None)
         return hist, n, d
 
     def done(self) -> np.ndarray:
-        self._check()
         d = np.zeros(self.B, np.uint8)
-        _lib.check(self.L.csm_read_codes(self.model.engine, None, None, _lib.ptr(d), None))
+        self._call("csm_read_codes", None, None, _lib.ptr(d), None)
         return d.astype(bool)
 
     def last_codes(self) -> np.ndarray:
-        self._check()
         out = np.zeros((self.B, self.model.n_audio_codebooks), np.int32)
-        _lib.check(self.L.csm_debug_read(self.model.engine, b"codes", _lib.ptr(out), out.nbytes, None))
+        self._call("csm_debug_read", b"codes", _lib.ptr(out), out.nbytes, None)
         return out
 
     def debug(self, what: str, shape) -> np.ndarray:
-        self._check()
         out = np.zeros(shape, np.float32)
-        _lib.check(self.L.csm_debug_read(self.model.engine, what.encode(), _lib.ptr(out), out.nbytes, None))
+        self._call("csm_debug_read", what.encode(), _lib.ptr(out), out.nbytes, None)
         return out
 
 
@@ -235,7 +252,7 @@ def generate_frame(model: CSM, tokens, *, temperature: float = 0.8, token_mask=N
 
     The rows are appended to the backbone KV held by ``cache`` (a fresh one when None),
     then one frame (c0 + 31 decoder steps) runs on the GPU.  With ``logits_processors`` the frame
-    pauses after codebook0_head for them (``FrameCache.run_processed``)."""
+    pauses after codebook0_head for them (``FrameCache.step`` picks the frame's mode)."""
     tokens = np.asarray(tokens, np.int32)
     mask = np.ones_like(tokens, dtype=bool) if token_mask is None else np.asarray(token_mask).astype(bool)
     B = tokens.shape[0]
@@ -250,17 +267,8 @@ def generate_frame(model: CSM, tokens, *, temperature: float = 0.8, token_mask=N
                              f"create the cache with make_frame_cache(model, temperature=..., sampler=...)")
     for b in range(B):
         cache.prefill(b, tokens[b], mask[b])
-    if isinstance(cache.sampler, HostSampler):
-        cache.run_host_sampled(cache.sampler, logits_processors or (), c0_history)
-        return cache.last_codes()
-    if logits_processors:
-        cache.run_processed(logits_processors, c0_history)
-        return cache.last_codes()
-    cache.run(1)
-    codes = cache.last_codes()
-    if c0_history is not None:
-        c0_history.append(codes[:, :1].copy())
-    return codes
+    cache.step(logits_processors, c0_history)
+    return cache.last_codes()
 
 
 def build_prompt(model: CSM, text, speaker: int, context: Sequence[Segment]):
@@ -283,9 +291,25 @@ def _check_window(model: CSM, L: int, max_audio_frames: int):
         raise ValueError(f"Inputs too long ({L}), must be below max_seq_len - max_audio_frames: {max_seq_len}")
 
 
+def _start(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], max_audio_frames: int, sampler, seeds,
+           logits_processors, batched_prefill: bool):
+    """What every frame loop begins with: the window guard on every prompt (before any engine call), a
+    ``FrameCache`` of one utterance per prompt with the processors the GPU takes (``device_processors``),
+    and the prompts' prefill -- one csm_prefill_batch pass, or csm_prefill of the only prompt.  Returns
+    (cache, the processors left for the host: None when the GPU took them)."""
+    for t, _ in prompts:
+        _check_window(model, t.shape[0], max_audio_frames)
+    on_device = device_processors(logits_processors, sampler)
+    cache = FrameCache(model, len(prompts), sampler, seeds, on_device)
+    if batched_prefill:
+        cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(prompts)])
+    else:
+        cache.prefill(0, *prompts[0])
+    return cache, (logits_processors if on_device is None else None)
+
+
 def _mark(timings: Optional[dict], key: str, t0: float, model: Optional[CSM] = None) -> float:
     """Phase timer (bench.py --phases): wait for the engine, add the elapsed wall time to timings[key]."""
-    import time
     if timings is None:
         return t0
     if model is not None:
@@ -304,31 +328,15 @@ def generate_codes_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndar
     (generation.py:44-49).
     ``timings`` (optional dict): wall seconds of the prompt prefill and of the frames are added to
     its "prefill" / "frames" entries (the engine is synchronized at each boundary)."""
-    import time
-    B = len(prompts)
-    for t, _ in prompts:
-        _check_window(model, t.shape[0], max_audio_frames)
     t0 = time.perf_counter()
-    on_device = device_processors(logits_processors, sampler)
-    if on_device is not None:
-        logits_processors = None
-    cache = FrameCache(model, B, sampler, seeds, on_device)
-    if B > 1:   # every prompt's rows through one pass of each projection (weights streamed once)
-        cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(prompts)])
-    else:
-        cache.prefill(0, *prompts[0])
+    # B > 1: every prompt's rows through one pass of each projection (weights streamed once)
+    cache, processors = _start(model, prompts, max_audio_frames, sampler, seeds, logits_processors, len(prompts) > 1)
     t0 = _mark(timings, "prefill", t0, model)
     left = max_audio_frames
-    if isinstance(sampler, HostSampler):  # a sampler callable: every code from the host, frame by frame
-        c0_history_h: list = []
-        for _ in range(max_audio_frames):
-            if cache.run_host_sampled(sampler, logits_processors or (), c0_history_h):
-                break
-        left = 0
-    elif logits_processors:
+    if isinstance(sampler, HostSampler) or processors:   # the host in every frame: frame by frame
         c0_history: list = []                                                    # generation.py:128
         for _ in range(max_audio_frames):
-            if cache.run_processed(logits_processors, c0_history):
+            if cache.step(processors, c0_history):
                 break
         left = 0
     while left > 0:
@@ -383,7 +391,6 @@ def generate_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]],
     """Batched extension: B prompts (tokens, mask) -> list of waveforms (or codes if decode=False;
     (codes, waveforms) with ``with_codes``).  ``timings``: per-phase wall seconds (prefill, frames,
     decode) added to the dict."""
-    import time
     smp = _resolve_sampler(temperature, sampler, top_k)
     hist, n_frames, _ = generate_codes_batch(model, prompts, int(max_audio_length_ms / 80), sampler=smp, seeds=seeds,
                                              timings=timings, logits_processors=logits_processors)
@@ -415,24 +422,32 @@ def _overlapped_frames(cache: "FrameCache", codec, max_audio_frames: int):
         yield codec.decode_step(prev[0])[:, 0], prev[1]
 
 
-def _host_sampled_frames(cache: "FrameCache", codec, max_audio_frames: int, sampler: HostSampler, processors):
-    """The streaming loop with a host sampler callable (every code from the host; nothing to overlap):
-    EOS is tested before the frame is decoded (generation.py:237-251)."""
+def _host_paced_frames(cache: "FrameCache", codec, max_audio_frames: int, processors):
+    """The streaming loop with the host in every frame -- a host sampler callable, or host logits
+    processors (lists ``device_processors`` turns down), for which the frame pauses after codebook0_head --
+    so there is nothing to overlap; EOS is tested before the frame is decoded (generation.py:237-251)."""
     c0_history: list = []
     for _ in range(max_audio_frames):
-        if cache.run_host_sampled(sampler, processors or (), c0_history):
+        if cache.step(processors, c0_history):
             break
         yield codec.decode_step(cache.last_codes())[:, 0], cache.done()
 
 
-def _processed_frames(cache: "FrameCache", codec, max_audio_frames: int, processors):
-    """The streaming loop with host logits processors (lists ``device_processors`` turns down): each frame pauses after codebook0_head, so
-    there is nothing to overlap; EOS is tested before the frame is decoded (generation.py:237-251)."""
-    c0_history: list = []
-    for _ in range(max_audio_frames):
-        if cache.run_processed(processors, c0_history):
-            break
-        yield codec.decode_step(cache.last_codes())[:, 0], cache.done()
+def _stream_frames(model: CSM, prompts, max_audio_frames: int, sampler, seeds, logits_processors,
+                   batched_prefill: bool):
+    """The body of both streaming entry points: ``_start``, then the mode's frame generator between two
+    resets of the codec's streaming state (the second also when the consumer closes the stream early)."""
+    codec = get_audio_tokenizer(model.n_audio_codebooks)
+    cache, processors = _start(model, prompts, max_audio_frames, sampler, seeds, logits_processors, batched_prefill)
+    B = len(prompts)
+    codec.reset_state(B)
+    try:
+        if isinstance(sampler, HostSampler) or processors:
+            yield from _host_paced_frames(cache, codec, max_audio_frames, processors)
+        else:
+            yield from _overlapped_frames(cache, codec, max_audio_frames)
+    finally:
+        codec.reset_state(B)
 
 
 def stream_generate_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]],
@@ -442,27 +457,8 @@ def stream_generate_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.nda
     """Batched extension of ``stream_generate`` (generation.py:181-258): per frame yields
     (pcm (B, 1920) float32 from the codec's streaming ``decode_step``, done (B,) bool).  An
     utterance's rows after its EOS frame are not audio (its ``done`` flag is set)."""
-    max_audio_frames = int(max_audio_length_ms / 80)
-    for t, _ in prompts:
-        _check_window(model, t.shape[0], max_audio_frames)
-    smp = _resolve_sampler(temperature, sampler, top_k)
-    B = len(prompts)
-    codec = get_audio_tokenizer(model.n_audio_codebooks)
-    on_device = device_processors(logits_processors, smp)
-    if on_device is not None:
-        logits_processors = None
-    cache = FrameCache(model, B, smp, seeds, on_device)
-    cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(prompts)])
-    codec.reset_state(B)
-    try:
-        if isinstance(smp, HostSampler):
-            yield from _host_sampled_frames(cache, codec, max_audio_frames, smp, logits_processors)
-        elif logits_processors:
-            yield from _processed_frames(cache, codec, max_audio_frames, logits_processors)
-        else:
-            yield from _overlapped_frames(cache, codec, max_audio_frames)
-    finally:
-        codec.reset_state(B)
+    yield from _stream_frames(model, prompts, int(max_audio_length_ms / 80),
+                              _resolve_sampler(temperature, sampler, top_k), seeds, logits_processors, True)
 
 
 def stream_generate(model: CSM, text, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
@@ -472,25 +468,9 @@ def stream_generate(model: CSM, text, speaker: int, context: List[Segment], max_
 
     Codec streaming state is per call (the reference resets a process-global Mimi,
     generation.py:224-225, :258)."""
-    max_audio_frames = int(max_audio_length_ms / 80)
-    t, m = build_prompt(model, text, speaker, context)
-    _check_window(model, t.shape[0], max_audio_frames)
-    smp = _resolve_sampler(temperature, sampler)
-    codec = get_audio_tokenizer(model.n_audio_codebooks)
-    on_device = device_processors(logits_processors, smp)
-    if on_device is not None:
-        logits_processors = None
-    cache = FrameCache(model, 1, smp, seed, on_device)
-    cache.prefill(0, t, m)
-    codec.reset_state(1)
-    try:
-        if isinstance(smp, HostSampler):
-            frames = _host_sampled_frames(cache, codec, max_audio_frames, smp, logits_processors)
-        elif logits_processors:
-            frames = _processed_frames(cache, codec, max_audio_frames, logits_processors)
-        else:
-            frames = _overlapped_frames(cache, codec, max_audio_frames)
+    prompt = build_prompt(model, text, speaker, context)
+    with contextlib.closing(_stream_frames(model, [prompt], int(max_audio_length_ms / 80),
+                                           _resolve_sampler(temperature, sampler), seed, logits_processors,
+                                           False)) as frames:     # (closed with this generator: the codec reset)
         for pcm, _ in frames:
             yield pcm[0]
-    finally:
-        codec.reset_state(1)

@@ -26,6 +26,9 @@ def _dims(m: MimiArgs) -> _lib.MimiDims:
                          m.norm_eps, 1 if m.gelu == "erf" else 0, 0 if m.attn_mode == "mlx" else 1)
 
 
+_SLOTS = "slots"    # MimiCodec._stream in slot mode (slot_reset)
+
+
 class MimiCodec:
     def __init__(self, m: MimiArgs, *, device: Optional[int] = None, max_batch: int = 1, max_frames: int = 1200):
         from .models import default_device
@@ -40,8 +43,7 @@ class MimiCodec:
         n_pos = 2 * max_frames * m.downsample_stride + 64
         t = mimi_rope_table(m, n_pos)
         _lib.check(L.mimi_set_rope_table(h, _lib.ptr(t), t.shape[0], t.shape[1] * 2))
-        self._stream_B = None
-        self._slots = False    # slot mode (slot_reset): decode_step is refused, not silently reset
+        self._stream = None    # the streaming state: None, the batch size of a decode_step stream, or _SLOTS
 
     def __del__(self):
         try:
@@ -96,14 +98,23 @@ class MimiCodec:
         if x.ndim == 3:
             x = x[:, 0, :]
         B, N = x.shape
+
+        def part(b0, nb, codes, got):
+            xb = np.ascontiguousarray(x[b0: b0 + nb])
+            return _lib.lib().mimi_encode(self._h, nb, N, _lib.ptr(xb), codes, got)
+        return self._encode_chunks(B, N, part)
+
+    def _encode_chunks(self, B: int, N: int, part) -> np.ndarray:
+        """The loop of both encodes: B clips of N samples in chunks of <= ``max_batch`` rows, each through
+        ``part(first row, rows, codes pointer, frame count pointer)``, its codes trimmed to the frames the
+        library reports."""
+        Tf = int(np.ceil(N / self.m.frame_size)) + 2
         out = []
         for b0 in range(0, B, self.max_batch):
-            xb = np.ascontiguousarray(x[b0: b0 + self.max_batch])
-            nb = xb.shape[0]
-            Tf = int(np.ceil(N / self.m.frame_size)) + 2
+            nb = min(self.max_batch, B - b0)
             codes = np.zeros((nb, self.m.n_q, Tf), np.int32)
             got = ctypes.c_int(0)
-            _lib.check(_lib.lib().mimi_encode(self._h, nb, N, _lib.ptr(xb), _lib.ptr(codes), ctypes.byref(got)))
+            _lib.check(part(b0, nb, _lib.ptr(codes), ctypes.byref(got)))
             out.append(codes.reshape(-1)[: nb * self.m.n_q * got.value].reshape(nb, self.m.n_q, got.value))
         return np.concatenate(out, 0)
 
@@ -114,17 +125,11 @@ class MimiCodec:
         if not xs or len({x.shape[0] for x in xs}) != 1:
             raise ValueError("encode_rows: same-length clips only")
         N = xs[0].shape[0]
-        out = []
-        for b0 in range(0, len(xs), self.max_batch):
-            part = xs[b0: b0 + self.max_batch]
-            nb = len(part)
-            ptrs = (ctypes.c_void_p * nb)(*[x.ctypes.data for x in part])
-            Tf = int(np.ceil(N / self.m.frame_size)) + 2
-            codes = np.zeros((nb, self.m.n_q, Tf), np.int32)
-            got = ctypes.c_int(0)
-            _lib.check(_lib.lib().mimi_encode_rows(self._h, nb, N, None, ptrs, _lib.ptr(codes), ctypes.byref(got)))
-            out.append(codes.reshape(-1)[: nb * self.m.n_q * got.value].reshape(nb, self.m.n_q, got.value))
-        return np.concatenate(out, 0)
+
+        def part(b0, nb, codes, got):
+            ptrs = (ctypes.c_void_p * nb)(*[x.ctypes.data for x in xs[b0: b0 + nb]])
+            return _lib.lib().mimi_encode_rows(self._h, nb, N, None, ptrs, codes, got)
+        return self._encode_chunks(len(xs), N, part)
 
     def decode(self, codes: np.ndarray) -> np.ndarray:
         """(B, n_q, F) int32 -> (B, 1, F*frame_size) float32.  Resets streaming state (moshi_mlx)."""
@@ -139,8 +144,7 @@ class MimiCodec:
             pcm = np.zeros((nb, F * self.m.frame_size), np.float32)
             _lib.check(_lib.lib().mimi_decode(self._h, nb, F, _lib.ptr(cb), 0, 0, _lib.ptr(pcm), 0))
             out.append(pcm)
-        self._stream_B = None
-        self._slots = False
+        self._stream = None
         return np.concatenate(out, 0)[:, None, :]
 
     def debug_rows(self) -> np.ndarray:
@@ -155,8 +159,7 @@ class MimiCodec:
 
     def reset_state(self, batch_size: int = 1):
         _lib.check(_lib.lib().mimi_reset_state(self._h, batch_size))
-        self._stream_B = batch_size
-        self._slots = False
+        self._stream = batch_size
 
     def decode_step(self, codes: np.ndarray) -> np.ndarray:
         """One frame: (B, n_q, 1) or (B, n_q) -> (B, 1, frame_size)."""
@@ -164,7 +167,7 @@ class MimiCodec:
         if c.ndim == 3:
             c = c[:, :, 0]
         B = c.shape[0]
-        if self._stream_B != B and not self._slots:
+        if self._stream not in (B, _SLOTS):    # (slot mode: refused by the library, not silently reset)
             self.reset_state(B)
         c = np.ascontiguousarray(c)
         pcm = np.zeros((B, self.m.frame_size), np.float32)
@@ -176,8 +179,7 @@ class MimiCodec:
         """Row b of the streaming state starts a new stream (mimi_slot_reset; enqueued, not waited for).  The
         first call puts the codec in slot mode, ``reset_state`` and ``decode`` leave it."""
         _lib.check(_lib.lib().mimi_slot_reset(self._h, int(b)))
-        self._stream_B = None
-        self._slots = True
+        self._stream = _SLOTS
 
     def decode_slots(self, hist, n: int, first_row: int, active, F_cap: Optional[int] = None,
                      on_device: bool = False) -> np.ndarray:

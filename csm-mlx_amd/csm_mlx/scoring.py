@@ -26,7 +26,6 @@ from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
 from .generation import FrameCache, _check_window
 from .sampling import Sampler
 
@@ -57,19 +56,16 @@ def score_frames(model, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], frames
     cache = FrameCache(model, B, Sampler(0.0, 0), [0] * B)
     for b, (t, m) in enumerate(prompts):
         cache.prefill(b, t, m)
-    L = _lib.lib()
     if not logits:
         ce = np.zeros((F, B, K), np.float32)
         for f in range(F):
-            codes = np.ascontiguousarray(forced[f])
-            _lib.check(L.csm_frame_forced(model.engine, _lib.ptr(codes), None, None, _lib.ptr(ce[f])))
+            cache.forced(forced[f], ce=ce[f])
         return np.ascontiguousarray(ce.transpose(1, 0, 2))
     out = np.zeros((B, F, K, V), np.float32)
     c0 = np.zeros((B, V), np.float32)
     ci = np.zeros((K - 1, B, V), np.float32)
     for f in range(F):
-        codes = np.ascontiguousarray(forced[f])
-        _lib.check(L.csm_frame_forced(model.engine, _lib.ptr(codes), _lib.ptr(c0), _lib.ptr(ci), None))
+        cache.forced(forced[f], c0, ci)
         out[:, f, 0] = c0
         out[:, f, 1:] = ci.transpose(1, 0, 2)
     return out
@@ -104,21 +100,20 @@ def _score_utterance(model, tokens: np.ndarray, masks: np.ndarray, r0: int, logi
     with their own mask.  Returns (S - r0, K, V) logits or (S - r0, K) cross entropies."""
     S, n_cb = tokens.shape
     K, V = n_cb - 1, model.n_audio_vocab
-    L = _lib.lib()
     cache = FrameCache(model, 1, Sampler(0.0, 0), [0])
     cache.prefill(0, tokens[:r0], masks[:r0])
     out = np.zeros((S - r0, K, V) if logits else (S - r0, K), np.float32)
     c0 = np.zeros((1, V), np.float32)
     ci = np.zeros((K - 1, 1, V), np.float32)
     for t in range(r0, S):
-        codes = np.ascontiguousarray(tokens[t, :K][None], np.int32)
+        codes = tokens[t, :K][None]
         if logits:
-            _lib.check(L.csm_frame_forced(model.engine, _lib.ptr(codes), _lib.ptr(c0), _lib.ptr(ci), None))
+            cache.forced(codes, c0, ci)
             out[t - r0, 0] = c0[0]
             out[t - r0, 1:] = ci[:, 0]
         else:
             ce = np.zeros((1, K), np.float32)
-            _lib.check(L.csm_frame_forced(model.engine, _lib.ptr(codes), None, None, _lib.ptr(ce)))
+            cache.forced(codes, ce=ce)
             out[t - r0] = ce[0]
         if t + 1 < S and not _standard_row(masks[t], K):
             cache.prefill(0, tokens[t:t + 1], masks[t:t + 1])   # row t with its own mask

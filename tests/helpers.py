@@ -326,3 +326,93 @@ def linear_err(y, y64, S):
     """Largest |y - y64| / S; an output whose S is 0 (an all-zero weight row: padding) must be exactly 0."""
     d = np.abs(np.asarray(y, np.float64) - y64)
     return np.where(S > 0, d / np.where(S > 0, S, 1.0), np.where(d > 0, np.inf, 0.0)).max()
+
+
+# ----------------------------------------------------------------------------- SlotBatch against a stub engine
+STUB_K = 4
+
+
+class StubEngine:
+    """The engine's side of a ``SlotBatch`` (csm_mlx.batching._EngineSlots' methods) as a small object that
+    records every call.  eos[seed] = the frame at which the utterance submitted with that seed produces its
+    all-zero frame (absent: never); a slot's codes are (seed + 1, its own frame index + 1, 1, 1).
+
+    ``StubEngine(slots, eos)`` is what ``SlotBatch.run`` may use: it has its own ``log``, logs ("run", n), and
+    its ``wait`` and ``ring`` fail -- ``run`` must not call them.  With ``F_cap`` (and a ``log`` to share with
+    a stub codec) it is the streaming engine: ``run`` writes the frames' codes into a ring [F_cap][B][K] over
+    the global frame index (every other cell written in a frame is -1) and logs ("run", n, global frame
+    index), ``wait`` is logged, ``ring`` hands out the stub itself as the "device pointer"; ``pending`` holds
+    from a ``run(n, sync=False)`` to its ``wait`` and no other call may fall inside."""
+
+    def __init__(self, slots, eos, F_cap=None, log=None):
+        self.B, self.eos, self.F_cap, self.log = slots, eos, F_cap, [] if log is None else log
+        self.seed = [None] * slots
+        self.frame = [0] * slots           # the slot's own frame index
+        self.n = [0] * slots
+        self.done = [True] * slots
+        self.prompt = [False] * slots
+        self.rows = [[] for _ in range(slots)]
+        self.hist = None if F_cap is None else np.full((F_cap, slots, STUB_K), -7, np.int32)
+        self.frames_run = 0
+        self.pending = False
+
+    def restart(self, b, seed):
+        assert not self.pending
+        self.log.append(("restart", b, seed))
+        self.seed[b], self.frame[b], self.n[b], self.done[b], self.prompt[b], self.rows[b] = seed, 0, 0, False, False, []
+
+    def release(self, b):
+        assert not self.pending
+        self.log.append(("release", b))
+        self.seed[b], self.done[b], self.n[b], self.prompt[b] = None, True, 0, True
+
+    def prefill(self, items):
+        self.log.append(("prefill", tuple(b for b, _, _ in items)))
+        for b, t, m in items:
+            assert self.seed[b] is not None and not self.prompt[b]
+            self.prompt[b] = True
+
+    def run(self, n, sync=True):
+        assert all(self.prompt), "frames while a restarted slot has no prompt"
+        assert not self.pending, "a chunk enqueued before the last one was waited for"
+        assert sync or self.hist is not None, "SlotBatch.run enqueues and waits in one call"
+        self.log.append(("run", n) if self.hist is None else ("run", n, self.frames_run))
+        for _ in range(n):
+            row = None
+            if self.hist is not None:
+                row = self.hist[self.frames_run % self.F_cap]
+                row[:] = -1
+            for b in range(self.B):
+                if self.seed[b] is None:
+                    continue
+                f = self.frame[b]
+                if not self.done[b]:
+                    if self.eos.get(self.seed[b]) == f:
+                        self.done[b] = True
+                    else:
+                        self.rows[b].append([self.seed[b] + 1, f + 1, 1, 1])
+                        if row is not None:
+                            row[b] = self.rows[b][-1]
+                        self.n[b] = f + 1
+                self.frame[b] = f + 1
+            self.frames_run += 1
+        self.pending = not sync
+
+    def wait(self):
+        assert self.hist is not None, "SlotBatch.run has nothing to wait for"
+        self.log.append(("wait",))
+        self.pending = False
+
+    def ring(self):
+        assert self.hist is not None, "SlotBatch.run reads no ring"
+        return self, self.F_cap, self.frames_run        # the "device pointer" is the stub itself
+
+    def poll(self):
+        assert not self.pending, "polled before the wait"
+        return np.array(self.n, np.int32), np.array(self.done, bool)
+
+    def read(self, b, cap):
+        assert not self.pending
+        self.log.append(("read", b))
+        assert self.n[b] <= cap
+        return np.array(self.rows[b], np.int32).reshape(-1, STUB_K)

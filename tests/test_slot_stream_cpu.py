@@ -4,82 +4,9 @@ the last chunk, the ValueErrors -- and the slot codec ABI's checks that need no 
 import numpy as np
 import pytest
 
-K = 4
+from helpers import STUB_K as K, StubEngine
+
 FS = 4          # the stub codec's samples per frame
-
-
-class StubEngine:
-    """tests/test_slots_cpu.py's stub with the streaming methods: ``run(n, sync=False)`` writes the frames'
-    codes into a ring [F_cap][B][K] over the global frame index, ``wait`` and ``ring`` are logged.  eos[seed]
-    = the frame at which that utterance produces its all-zero frame; a slot's codes are
-    (seed + 1, its own frame index + 1, 1, 1), every other ring cell written in a frame is -1."""
-
-    def __init__(self, slots, eos, F_cap, log):
-        self.B, self.eos, self.F_cap, self.log = slots, eos, F_cap, log
-        self.seed = [None] * slots
-        self.frame = [0] * slots
-        self.n = [0] * slots
-        self.done = [True] * slots
-        self.prompt = [False] * slots
-        self.rows = [[] for _ in range(slots)]
-        self.hist = np.full((F_cap, slots, K), -7, np.int32)
-        self.frames_run = 0
-        self.pending = False
-
-    def restart(self, b, seed):
-        assert not self.pending
-        self.log.append(("restart", b, seed))
-        self.seed[b], self.frame[b], self.n[b], self.done[b], self.prompt[b], self.rows[b] = seed, 0, 0, False, False, []
-
-    def release(self, b):
-        assert not self.pending
-        self.log.append(("release", b))
-        self.seed[b], self.done[b], self.n[b], self.prompt[b] = None, True, 0, True
-
-    def prefill(self, items):
-        self.log.append(("prefill", tuple(b for b, _, _ in items)))
-        for b, t, m in items:
-            assert self.seed[b] is not None and not self.prompt[b]
-            self.prompt[b] = True
-
-    def run(self, n, sync=True):
-        assert all(self.prompt), "frames while a restarted slot has no prompt"
-        assert not self.pending, "a chunk enqueued before the last one was waited for"
-        self.log.append(("run", n, self.frames_run))
-        for _ in range(n):
-            row = self.hist[self.frames_run % self.F_cap]
-            row[:] = -1
-            for b in range(self.B):
-                if self.seed[b] is None:
-                    continue
-                f = self.frame[b]
-                if not self.done[b]:
-                    if self.eos.get(self.seed[b]) == f:
-                        self.done[b] = True
-                    else:
-                        self.rows[b].append([self.seed[b] + 1, f + 1, 1, 1])
-                        row[b] = self.rows[b][-1]
-                        self.n[b] = f + 1
-                self.frame[b] = f + 1
-            self.frames_run += 1
-        self.pending = not sync
-
-    def wait(self):
-        self.log.append(("wait",))
-        self.pending = False
-
-    def ring(self):
-        return self, self.F_cap, self.frames_run        # the "device pointer" is the stub itself
-
-    def poll(self):
-        assert not self.pending, "polled before the wait"
-        return np.array(self.n, np.int32), np.array(self.done, bool)
-
-    def read(self, b, cap):
-        assert not self.pending
-        self.log.append(("read", b))
-        assert self.n[b] <= cap
-        return np.array(self.rows[b], np.int32).reshape(-1, K)
 
 
 class StubCodec:

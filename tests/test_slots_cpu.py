@@ -3,59 +3,7 @@ scripted EOS frames -- and the slot ABI's argument checks that need no GPU."""
 import numpy as np
 import pytest
 
-K = 4
-
-
-class StubEngine:
-    """Records every call.  eos[seed] = the frame at which the utterance submitted with that seed produces
-    its all-zero frame (absent: never); a slot's codes are (seed, its own frame index, 0, 0) + 1."""
-
-    def __init__(self, slots, eos):
-        self.B, self.eos, self.log = slots, eos, []
-        self.seed = [None] * slots
-        self.frame = [0] * slots           # the slot's own frame index
-        self.n = [0] * slots
-        self.done = [True] * slots
-        self.prompt = [False] * slots
-        self.rows = [[] for _ in range(slots)]
-
-    def restart(self, b, seed):
-        self.log.append(("restart", b, seed))
-        self.seed[b], self.frame[b], self.n[b], self.done[b], self.prompt[b], self.rows[b] = seed, 0, 0, False, False, []
-
-    def release(self, b):
-        self.log.append(("release", b))
-        self.seed[b], self.done[b], self.n[b], self.prompt[b] = None, True, 0, True
-
-    def prefill(self, items):
-        self.log.append(("prefill", tuple(b for b, _, _ in items)))
-        for b, t, m in items:
-            assert self.seed[b] is not None and not self.prompt[b]
-            self.prompt[b] = True
-
-    def run(self, n):
-        assert all(self.prompt), "frames while a restarted slot has no prompt"
-        self.log.append(("run", n))
-        for _ in range(n):
-            for b in range(self.B):
-                if self.seed[b] is None:
-                    continue
-                f = self.frame[b]
-                if not self.done[b]:
-                    if self.eos.get(self.seed[b]) == f:
-                        self.done[b] = True
-                    else:
-                        self.rows[b].append([self.seed[b] + 1, f + 1, 1, 1])
-                        self.n[b] = f + 1
-                self.frame[b] = f + 1
-
-    def poll(self):
-        return np.array(self.n, np.int32), np.array(self.done, bool)
-
-    def read(self, b, cap):
-        self.log.append(("read", b))
-        assert self.n[b] <= cap
-        return np.array(self.rows[b], np.int32).reshape(-1, K)
+from helpers import STUB_K as K, StubEngine
 
 
 def handle():
