@@ -142,8 +142,8 @@ B32_PROJ = 4                        # random unit vectors per streamed chunk's p
 
 def _b32_prompts():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from helpers import prompt_ids
-    return [text_frame(prompt_ids(1 if g == 0 else 1000 + g), 32) for g in range(32)]
+    from helpers import b32_prompt_ids
+    return [text_frame(ids, 32) for ids in b32_prompt_ids()]
 
 
 def _b32_run(frames, temperature=0.0, top_k=0, keep_logits=True):

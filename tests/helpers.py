@@ -92,9 +92,32 @@ def prompt_ids(seed: int, n_mid: int = 12, vocab: int = 128000, bos: int = 12800
     return [bos] + [int(x) for x in rng.integers(0, vocab, n_mid)] + [eos]
 
 
+def b32_prompt_ids():
+    """The ids of configs[3]'s 32 utterances: tests/test_batched_long_gpu.py runs them, tests/golden/make_golden.py
+    computed their fixtures -- one list, so the two cannot part."""
+    return [prompt_ids(1 if g == 0 else 1000 + g) for g in range(32)]
+
+
 def tiny_prompt_ids(seed: int, n_mid: int = 5):
     rng = np.random.default_rng(seed)
     return [998] + [int(x) for x in rng.integers(0, 990, n_mid)] + [999]
+
+
+def rms(a, b):
+    """Root mean square of a - b over every element (0 for empty arrays); the shapes must agree."""
+    a, b = np.asarray(a, np.float64).reshape(-1), np.asarray(b, np.float64).reshape(-1)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    return float(np.sqrt(np.mean((a - b) ** 2))) if a.size else 0.0
+
+
+def free_port():
+    """A TCP port that was free a moment ago (the multi-process tests' rendezvous)."""
+    import socket
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
 
 
 def first_divergence(a: np.ndarray, b: np.ndarray):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from helpers import csm_weights, make_adapters, oracle_for, tiny_prompt_ids, write_adapter_dir
+from rigs import build_model
 from test_csm_gpu import _compare, _engine_frames, _oracle_frames
 
 pytestmark = pytest.mark.gpu
@@ -41,10 +42,7 @@ def test_tiny_adapters_greedy_parity(tmp_path, ftype, keys, source):
 
 def test_adapters_on_q4_engine_refused(tmp_path):
     from csm_mlx import load_adapters
-    from csm_mlx.models import CSM
-    args, w = csm_weights("tiny")
-    model = CSM(args, dtype="q4")
-    model.load_weights(w)
+    args, w, model = build_model("tiny", "q4")
     cfg, tensors, _ = make_adapters(model, w, "lora", ("attn",))
     with pytest.raises(NotImplementedError):
         load_adapters(model, str(write_adapter_dir(tmp_path / "a", cfg, tensors)))

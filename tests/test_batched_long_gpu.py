@@ -18,33 +18,23 @@ The first two run on the EOS-capable rig of the seed-0 weights (tests/helpers.py
 different frames (per-utterance EOS at B > 1, generation.py:139-161).  Bars: codes and frame counts
 bit-exact; logits within 2e-3 x max|logit|; chunks within 1e-4 RMS (statistics: within what a 1e-4
 RMS error allows)."""
-import os
-
 import numpy as np
 import pytest
 
-from helpers import eos_weights, first_divergence
+from helpers import b32_prompt_ids, eos_weights, first_divergence
+from rigs import build_model, fixture as _fixture, frame_taps
 
 pytestmark = pytest.mark.gpu
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NEAR_TIE = 1e-5   # oracle top-2 logit margin / max|logit| below which a code is a tie at fp32 resolution
-
-
-def _fixture(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
 
 
 def _prompts():
     from csm_mlx.tokenizers import tokenize_text_segment
-    from helpers import prompt_ids
-    return [tokenize_text_segment(prompt_ids(1 if g == 0 else 1000 + g), 0, 32) for g in range(32)]
+    return [tokenize_text_segment(ids, 0, 32) for ids in b32_prompt_ids()]
 
 
 def _model(args, w, B):
-    from csm_mlx.models import CSM
-    m = CSM(args, dtype="bf16", max_batch=B)
-    m.load_weights(w)
-    return m
+    return build_model((args, w), "bf16", B)[2]
 
 
 def _check_codes(hist, n, z):
@@ -61,31 +51,27 @@ def _check_codes(hist, n, z):
 
 
 def test_config4_shard_b32_greedy_125_frames():
-    from csm_mlx.generation import FrameCache
     from csm_mlx.sampling import Sampler
     z = _fixture("config4_b32_greedy_125.npz")
     args, w = eos_weights("1b")
-    B, K, V = 32, args.n_audio_codebooks, args.n_audio_vocab
-    Vp = (V + 7) // 8 * 8
+    B = 32
     model = _model(args, w, B)
-    cache = FrameCache(model, B, Sampler(0.0, 0), [0] * B)
-    cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(_prompts())])
     keep = {int(f): i for i, f in enumerate(z["frames"])}
     ref_n = z["n_frames"]
     eos_at = {int(ref_n[b]): [] for b in z["eos_utts"]}
     for b in z["eos_utts"]:
         eos_at[int(ref_n[b])].append(int(b))
+    read = sorted(f for f in set(keep) | set(eos_at) if f < 125)
+    hist, n, taps = frame_taps(model, _prompts(), 125, Sampler(0.0, 0), [0] * B, ("c0_logits", "ci_logits"),
+                               keep=set(read), prefill_batch=True)
+    del model
     cis = [c - 1 for c in z["ci_codebooks"]]
     errs = []
-    for f in range(125):
-        cache.run(1)
-        if f in keep or f in eos_at:
-            c0 = cache.debug("c0_logits", (B, Vp))[:, :V]
+    for f, c0, ci in zip(read, taps["c0_logits"], taps["ci_logits"]):
         if f in keep:
-            ci = cache.debug("ci_logits", (K - 1, B, Vp))[:, :, :V]
             i = keep[f]
             for j, b in enumerate(z["logit_utts"]):            # (utterances that run all 125 frames)
-                for got, want in ((c0[b], z["c0"][i, j]), (ci[cis, b], z["ci"][i, j])):
+                for got, want in ((c0[b], z["c0"][i, j]), (ci[b, cis], z["ci"][i, j])):
                     err = float(np.abs(got - want).max())
                     if err > 2e-3 * float(np.abs(want).max()):
                         errs.append(f"frame {f} utterance {b}: logits err {err:.3e}")
@@ -94,8 +80,6 @@ def test_config4_shard_b32_greedy_125_frames():
             err = float(np.abs(c0[b] - z["eos_c0"][j]).max())
             if err > 2e-3 * float(np.abs(z["eos_c0"][j]).max()):
                 errs.append(f"EOS frame {f} utterance {b}: c0 logits err {err:.3e}")
-    hist, n, _ = cache.codes()
-    del model
     _check_codes(hist, n, z)
     assert not errs, "; ".join(errs[:10])
 
@@ -175,17 +159,12 @@ def test_config5_q4_b64_greedy_125_frames():
     * c0 / ci logits of the first and last pinned utterance at frames 0 / 64 / 124 within 1e-3 x max|logit|
       (the int4 bar of test_gemm_gpu.py) where that utterance's prompt is the oracle's."""
     import bench
-    from csm_mlx.generation import FrameCache
-    from csm_mlx.models import CSM
     from csm_mlx.sampling import Sampler
-    from helpers import csm_weights
     from test_configs_gpu import _codec
     z = _fixture("config5_q4_b16_greedy_125.npz")
-    args, w = csm_weights("1b")
-    B, K, V = 64, args.n_audio_codebooks, args.n_audio_vocab
-    Vp = (V + 7) // 8 * 8
-    model = CSM(args, dtype="q4", max_batch=B)
-    model.load_weights(w)
+    B = 64
+    args, w, model = build_model("1b", "q4", B)
+    K = args.n_audio_codebooks
     _codec(3 * B)
     mine = list(range(B))
     prompts = bench.context_prompts(mine, bench.context_segments(mine))
@@ -199,25 +178,20 @@ def test_config5_q4_b64_greedy_125_frames():
             flips.append((g,) + exp[g][3][1:])
     print("config 5 context codes the GPU encode takes at an RVQ near-tie (utterance, segment, codebook, frame, "
           "oracle margin):", flips, flush=True)
-    cache = FrameCache(model, B, Sampler(0.0, 0), [0] * B)
-    cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(prompts)])
     keep = {int(f): i for i, f in enumerate(z["frames"])}
     logit_utts = [(j, utts[int(u)]) for j, u in enumerate(z["logit_utts"]) if exp[utts[int(u)]][3] is None]
     assert logit_utts, "no logit utterance ran the oracle's own prompt"
+    hist, n, taps = frame_taps(model, prompts, 125, Sampler(0.0, 0), [0] * B, ("c0_logits", "ci_logits"),
+                               keep=set(keep), prefill_batch=True)
+    del model
     cis = [c - 1 for c in z["ci_codebooks"]]
     errs = []
-    for f in range(125):
-        cache.run(1)
-        if f in keep:
-            c0 = cache.debug("c0_logits", (B, Vp))[:, :V]
-            ci = cache.debug("ci_logits", (K - 1, B, Vp))[:, :, :V]
-            for j, g in logit_utts:
-                for got, want in ((c0[g], z["c0"][j, keep[f]]), (ci[cis, g], z["ci"][j, keep[f]])):
-                    err = float(np.abs(got - want).max())
-                    if err > 1e-3 * float(np.abs(want).max()):
-                        errs.append(f"frame {f} utterance {g}: logits err {err:.3e}")
-    hist, n, _ = cache.codes()
-    del model
+    for f, c0, ci in zip(sorted(f for f in keep if f < 125), taps["c0_logits"], taps["ci_logits"]):
+        for j, g in logit_utts:
+            for got, want in ((c0[g], z["c0"][j, keep[f]]), (ci[g, cis], z["ci"][j, keep[f]])):
+                err = float(np.abs(got - want).max())
+                if err > 1e-3 * float(np.abs(want).max()):
+                    errs.append(f"frame {f} utterance {g}: logits err {err:.3e}")
     bad, ties = [], []
     for g in utts:
         codes, nb, margin, _ = exp[g]

@@ -9,53 +9,29 @@ step must run for every frame, be deterministic and leave no hand-off timeout be
 import numpy as np
 import pytest
 
-from helpers import csm_weights, first_divergence, oracle_for, prompt_ids
+from helpers import first_divergence, oracle_for, prompt_ids
+from rigs import ab, build_model, frame_taps, handoffs, set_option, synchronize
 
 pytestmark = pytest.mark.gpu
 
 
 def _run(model, prompt, frames):
-    from csm_mlx.generation import FrameCache
     from csm_mlx.sampling import Sampler
-    V = model.n_audio_vocab
-    Vp = (V + 7) // 8 * 8
-    cache = FrameCache(model, 1, Sampler(0.0, 0), [0])
-    cache.prefill(0, *prompt)
-    logs = []
-    for _ in range(frames):
-        cache.run(1)
-        logs.append(cache.debug("c0_logits", (1, Vp))[0, :V])
-    hist, n, _ = cache.codes()
-    return hist[: n[0], 0], logs
-
-
-def _epoch(L, model):
-    from csm_mlx import _lib
-    ep = np.zeros(1, np.uint32)
-    _lib.check(L.csm_debug_read(model.engine, b"bb_step_epoch", _lib.ptr(ep), 4, None))
-    return int(ep[0])
+    hist, n, taps = frame_taps(model, [prompt], frames, Sampler(0.0, 0), [0], ("c0_logits",))
+    return hist[: n[0], 0], taps["c0_logits"][:, 0]
 
 
 @pytest.fixture(scope="module")
 def model_1b():
-    from csm_mlx.models import CSM
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype="bf16")
-    model.load_weights(w)
+    args, w, model = build_model("1b", "bf16")
     yield args, w, model
     del model
 
 
-def _compare(model, prompt, frames, check_oracle=None):
-    from csm_mlx import _lib
-    L = _lib.lib()
-    _lib.check(L.csm_set_option(model.engine, b"bb_step", 0))
-    ref, ref_logs = _run(model, prompt, frames)
-    _lib.check(L.csm_set_option(model.engine, b"bb_step", 1))
-    e0 = _epoch(L, model)
-    got, got_logs = _run(model, prompt, frames)
+def _compare(model, prompt, frames):
     # the prompt prefill yields the first frame's h_last; every later frame runs one backbone step
-    assert _epoch(L, model) - e0 == (frames - 1) * 80, "the persistent backbone step did not run every frame"
+    (ref, ref_logs), (got, got_logs) = ab(model, "bb_step", lambda: _run(model, prompt, frames),
+                                          (frames - 1) * handoffs("bb_step", model.n_audio_codebooks))
     assert first_divergence(got, ref) is None, f"bb_step codes differ from the launch path at {first_divergence(got, ref)}"
     for f, (a, b) in enumerate(zip(got_logs, ref_logs)):
         assert np.abs(a - b).max() <= 2e-3 * np.abs(b).max(), f"frame {f}: c0 logits differ"
@@ -106,7 +82,7 @@ def test_handoff_timeout_reported_by_every_frame_entry(model_1b):
         cache.run(1)                                      # the next frame starts with a backbone step
         if entry == "finish":
             _lib.check(L.csm_frame_c0_logits(model.engine, _lib.ptr(logits)))
-        _lib.check(L.csm_set_option(model.engine, b"inject_handoff_error", 1))
+        set_option(model, "inject_handoff_error", 1)
         with pytest.raises(_lib.CsmHipError, match="hand-off wait timed out"):
             if entry == "forced":
                 _lib.check(L.csm_frame_forced(model.engine, _lib.ptr(codes), None, None, None))
@@ -114,15 +90,12 @@ def test_handoff_timeout_reported_by_every_frame_entry(model_1b):
                 _lib.check(L.csm_frame_c0_logits(model.engine, _lib.ptr(logits)))
             else:
                 _lib.check(L.csm_frame_finish(model.engine, _lib.ptr(logits), None))
-        _lib.check(L.csm_synchronize(model.engine))       # the flag was consumed by the report
+        synchronize(model)                                # the flag was consumed by the report
 
 
 @pytest.fixture(scope="module")
 def model_1b_q4():
-    from csm_mlx.models import CSM
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype="q4")
-    model.load_weights(w)
+    args, w, model = build_model("1b", "q4")
     yield args, w, model
     del model
 

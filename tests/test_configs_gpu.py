@@ -11,7 +11,8 @@
 import numpy as np
 import pytest
 
-from helpers import csm_weights, first_divergence, oracle_batch, oracle_for, prompt_ids
+from helpers import first_divergence, oracle_batch, oracle_for, prompt_ids
+from rigs import build_model, set_option
 
 pytestmark = pytest.mark.gpu
 
@@ -43,13 +44,10 @@ def _engine_codes(model, B):
 
 def test_config2_stream_generate_batch_sampled():
     from csm_mlx.generation import stream_generate_batch
-    from csm_mlx.models import CSM
     from csm_mlx.tokenizers import tokenize_text_segment
     from oracle.mimi_oracle import OracleMimi
     B, frames = 32, 3
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype="bf16", max_batch=B)
-    model.load_weights(w)
+    args, w, model = build_model("1b", "bf16", max_batch=B)
     codec, mc, mw = _codec(B)
     prompts = [tokenize_text_segment(prompt_ids(1000 + b), 0, 32) for b in range(B)]
     seeds = [1234 + b for b in range(B)]
@@ -72,16 +70,13 @@ def test_config2_stream_generate_batch_sampled():
 
 def test_config4_q4_context_segments():
     from csm_mlx.generation import generate_codes_batch
-    from csm_mlx.models import CSM
     from csm_mlx.sampling import Sampler
     from csm_mlx.segment import Segment
     from csm_mlx.tokenizers import tokenize_segments_batch, tokenize_text_segment
     from oracle.mimi_oracle import OracleMimi
     import bench
     B, frames = 4, 2
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype="q4", max_batch=B)     # bench.py --config 5: float weights quantized on load
-    model.load_weights(w)
+    args, w, model = build_model("1b", "q4", max_batch=B)     # bench.py --config 5: float weights quantized on load
     codec, mc, mw = _codec(3 * B)
     segs = [Segment(s % 2, prompt_ids(10_000 + 10 * g + s), bench.context_audio(g, s)) for g in range(B) for s in range(3)]
     enc = tokenize_segments_batch(segs, n_audio_codebooks=32)
@@ -107,18 +102,13 @@ def test_config5_multi_group_prefill():
     tables bench.py --config 5 runs (B = 64: 8 groups).  Both against csm_prefill per utterance
     (h_last within the int4 bar, the first 2 frames' codes identical) and against the oracle on the
     dequantized weights for utterances 0, 7 (last of group 1) and 8 (group 2 alone)."""
-    import ctypes
-    from csm_mlx import _lib
     from csm_mlx.generation import FrameCache
-    from csm_mlx.models import CSM
     from csm_mlx.sampling import Sampler
     from csm_mlx.segment import Segment
     from csm_mlx.tokenizers import tokenize_segments_batch, tokenize_text_segment
     import bench
     B, frames = 9, 2
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype="q4", max_batch=B)
-    model.load_weights(w)
+    args, w, model = build_model("1b", "q4", max_batch=B)
     _codec(3 * B)
     segs = [Segment(s % 2, prompt_ids(10_000 + 10 * g + s), bench.context_audio(g, s)) for g in range(B) for s in range(3)]
     enc = tokenize_segments_batch(segs, n_audio_codebooks=32)
@@ -127,11 +117,10 @@ def test_config5_multi_group_prefill():
         parts = enc[3 * g:3 * g + 3] + [tokenize_text_segment(prompt_ids(g), 0, 32)]
         prompts.append((np.concatenate([t for t, _ in parts]), np.concatenate([m for _, m in parts])))
     assert sum(t.shape[0] for t, _ in prompts) > 2048
-    L = _lib.lib()
     D = model.backbone.args.hidden_size
 
     def run(mode):
-        _lib.check(L.csm_set_option(model.engine, b"prefill_rows", 500 if mode == "cap500" else 0))
+        set_option(model, "prefill_rows", 500 if mode == "cap500" else 0)
         cache = FrameCache(model, B, Sampler(0.0, 0), [0] * B)
         if mode == "single":
             for b, (t, m) in enumerate(prompts):
@@ -146,7 +135,7 @@ def test_config5_multi_group_prefill():
     h1, c1, n1 = run("single")
     h2, c2, n2 = run("default")
     h3, c3, n3 = run("cap500")
-    _lib.check(L.csm_set_option(model.engine, b"prefill_rows", 0))
+    set_option(model, "prefill_rows", 0)
     del model
     for h, c, n, tag in ((h2, c2, n2, "2 groups"), (h3, c3, n3, "5 groups")):
         err = np.abs(h - h1).max(axis=1) / np.abs(h1).max(axis=1)

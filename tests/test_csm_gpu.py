@@ -9,15 +9,13 @@ import numpy as np
 import pytest
 
 from helpers import csm_weights, first_divergence, oracle_for, prompt_ids, tiny_prompt_ids
+from rigs import build_model, frame_taps, set_option
 
 pytestmark = pytest.mark.gpu
 
 
 def _model(args, weights, dtype, max_batch=1):
-    from csm_mlx.models import CSM
-    m = CSM(args, dtype=dtype, max_batch=max_batch)
-    m.load_weights(weights)
-    return m
+    return build_model((args, weights), dtype, max_batch)[2]
 
 
 @pytest.fixture(scope="module")
@@ -32,23 +30,11 @@ def _oracle_frames(o, ids, frames, K, temperature=0.0, top_k=0, seed=0):
 
 
 def _engine_frames(model, ids, frames, temperature=0.0, top_k=0, seed=0):
-    from csm_mlx.generation import FrameCache
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
-    t, m = tokenize_text_segment(ids, 0, model.n_audio_codebooks)
-    cache = FrameCache(model, 1, Sampler(temperature, top_k), [seed])
-    cache.prefill(0, t, m)
-    logs = []
-    V = model.n_audio_vocab
-    Vp = (V + 7) // 8 * 8
-    K = model.n_audio_codebooks
-    for _ in range(frames):
-        cache.run(1)
-        c0 = cache.debug("c0_logits", (1, Vp))[0, :V]
-        ci = cache.debug("ci_logits", (K - 1, 1, Vp))[:, 0, :V]
-        logs.append((c0, ci))
-    hist, n, done = cache.codes()
-    return hist[:, 0], n[0], logs
+    prompt = tokenize_text_segment(ids, 0, model.n_audio_codebooks)
+    hist, n, taps = frame_taps(model, [prompt], frames, Sampler(temperature, top_k), [seed], ("c0_logits", "ci_logits"))
+    return hist[:, 0], n[0], list(zip(taps["c0_logits"][:, 0], taps["ci_logits"][:, 0]))
 
 
 def _compare(eng, orc, frames, rtol):
@@ -178,7 +164,6 @@ def test_csm_1b_first_frames(dtype):
 def test_folded_layer0_qkv_table_matches_gemv(tiny, which, dtype):
     """Decoder steps >= 2 gather layer 0's (RoPE'd q, k | v) from the table built at csm_begin by the
     same QKV GEMV: codes must be bit-identical to running the GEMV every step."""
-    from csm_mlx import _lib
     from csm_mlx.generation import generate_codes_batch
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
@@ -187,11 +172,10 @@ def test_folded_layer0_qkv_table_matches_gemv(tiny, which, dtype):
     K = args.n_audio_codebooks
     ids = [tiny_prompt_ids(40 + b, 3 + b) if which == "tiny" else prompt_ids(40 + b) for b in range(2)]
     prompts = [tokenize_text_segment(i, 0, K) for i in ids]
-    L = _lib.lib()
     frames = 12 if which == "tiny" else 6
-    _lib.check(L.csm_set_option(model.engine, b"qkv0_tab", 0))
+    set_option(model, "qkv0_tab", 0)
     ref, n_ref, _ = generate_codes_batch(model, prompts, frames, sampler=Sampler(0.0, 0))
-    _lib.check(L.csm_set_option(model.engine, b"qkv0_tab", 1))
+    set_option(model, "qkv0_tab", 1)
     got, n_got, _ = generate_codes_batch(model, prompts, frames, sampler=Sampler(0.0, 0))
     assert np.array_equal(n_got, n_ref)
     assert np.array_equal(got, ref), f"first diff at {np.argwhere(got != ref)[0]}"
@@ -203,7 +187,6 @@ def test_unfolded_projection_matches_oracle(tiny, dtype):
     """fold_proj off: at codebook steps >= 2 the projection GEMV gathers its input row from audio_emb in
     the weight's own type (float32 / bf16 / int4) instead of reading the folded fp32 table -- the gather
     branch no other test reaches past step 1.  Greedy codes bit-exact against the oracle."""
-    from csm_mlx import _lib
     from csm_mlx.generation import generate_codes_batch
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
@@ -213,7 +196,7 @@ def test_unfolded_projection_matches_oracle(tiny, dtype):
     model = _model(args, w, dtype, max_batch=2)
     o = oracle_for(args, w, bf16=(dtype == "bf16"), q4=(dtype == "q4"))
     id_sets = [tiny_prompt_ids(40 + b, 3 + b) for b in range(2)]
-    _lib.check(_lib.lib().csm_set_option(model.engine, b"fold_proj", 0))
+    set_option(model, "fold_proj", 0)
     hist, n, _ = generate_codes_batch(model, [tokenize_text_segment(i, 0, K) for i in id_sets], 12,
                                       sampler=Sampler(0.0, 0))
     for b, ids in enumerate(id_sets):

@@ -8,24 +8,16 @@ leave no hand-off timeout behind.  (tests/test_long_gpu.py's 125-frame bf16 fixt
 import numpy as np
 import pytest
 
-from helpers import csm_weights, first_divergence, oracle_for, prompt_ids
+from helpers import first_divergence, oracle_for, prompt_ids
+from rigs import ab, build_model, codes_per_utterance, epoch, frame_taps, handoffs, set_option
 
 pytestmark = pytest.mark.gpu
 
 
 def _run(model, prompt, frames):
-    from csm_mlx.generation import FrameCache
     from csm_mlx.sampling import Sampler
-    V, K = model.n_audio_vocab, model.n_audio_codebooks
-    Vp = (V + 7) // 8 * 8
-    cache = FrameCache(model, 1, Sampler(0.0, 0), [0])
-    cache.prefill(0, *prompt)
-    logs = []
-    for _ in range(frames):
-        cache.run(1)
-        logs.append((cache.debug("c0_logits", (1, Vp))[0, :V], cache.debug("ci_logits", (K - 1, 1, Vp))[:, 0, :V]))
-    hist, n, _ = cache.codes()
-    return hist[: n[0], 0], logs
+    hist, n, taps = frame_taps(model, [prompt], frames, Sampler(0.0, 0), [0], ("c0_logits", "ci_logits"))
+    return hist[: n[0], 0], list(zip(taps["c0_logits"][:, 0], taps["ci_logits"][:, 0]))
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "q4"])
@@ -33,25 +25,12 @@ def test_dec_frame_matches_launch_path_and_oracle(dtype):
     """q4: dec_frame_kernel<true> (an nn.quantize'd engine: int4 nibbles + group affine words for every
     decoder projection, codebook0_head and the projection; audio_head bf16) against the int4 GEMV launch
     path and the oracle on the dequantized weights."""
-    from csm_mlx import _lib
     from csm_mlx.generation import generate_codes_batch
-    from csm_mlx.models import CSM
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype=dtype)
-    model.load_weights(w)
-    L = _lib.lib()
+    args, w, model = build_model("1b", dtype)
     prompt = tokenize_text_segment(prompt_ids(31), 0, 32)
-    _lib.check(L.csm_set_option(model.engine, b"dec_frame", 0))
-    ref, ref_logs = _run(model, prompt, 12)
-    _lib.check(L.csm_set_option(model.engine, b"dec_frame", 1))
-    ep0 = np.zeros(1, np.uint32)
-    _lib.check(L.csm_debug_read(model.engine, b"dec_frame_epoch", _lib.ptr(ep0), 4, None))
-    got, got_logs = _run(model, prompt, 12)
-    ep1 = np.zeros(1, np.uint32)
-    _lib.check(L.csm_debug_read(model.engine, b"dec_frame_epoch", _lib.ptr(ep1), 4, None))
-    assert int(ep1[0]) - int(ep0[0]) == 12 * 498, "the persistent frame decoder did not run every frame"
+    (ref, ref_logs), (got, got_logs) = ab(model, "dec_frame", lambda: _run(model, prompt, 12), 12 * handoffs("dec_frame", args.n_audio_codebooks))
     assert first_divergence(got, ref) is None, f"dec_frame codes differ from the launch path at {first_divergence(got, ref)}"
     for f, ((c0a, cia), (c0b, cib)) in enumerate(zip(got_logs, ref_logs)):
         for a, b in ((c0a, c0b), (cia, cib)):
@@ -73,30 +52,15 @@ def test_dec_frame_sampled_matches_launch_path_and_oracle(top_k, dtype):
     to every workgroup, which runs sample_kernel's top-k radix select + Gumbel-max.  12 frames: codes
     identical to the launch path (sample_kernel) and to the oracle's restatement of the counter-based
     RNG; the decoder ran every frame (same 498 hand-offs as greedy)."""
-    from csm_mlx import _lib
-    from csm_mlx.generation import FrameCache, generate_codes_batch
-    from csm_mlx.models import CSM
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype=dtype)
-    model.load_weights(w)
-    L = _lib.lib()
+    args, w, model = build_model("1b", dtype)
     prompt = tokenize_text_segment(prompt_ids(33), 0, 32)
     smp, seed, frames = Sampler(0.8, top_k), 4242, 12
 
     def run():
-        h, n, _ = generate_codes_batch(model, [prompt], frames, sampler=smp, seeds=[seed])
-        return h[: n[0], 0].copy()
-    _lib.check(L.csm_set_option(model.engine, b"dec_frame", 0))
-    ref = run()
-    _lib.check(L.csm_set_option(model.engine, b"dec_frame", 1))
-    ep0 = np.zeros(1, np.uint32)
-    _lib.check(L.csm_debug_read(model.engine, b"dec_frame_epoch", _lib.ptr(ep0), 4, None))
-    got = run()
-    ep1 = np.zeros(1, np.uint32)
-    _lib.check(L.csm_debug_read(model.engine, b"dec_frame_epoch", _lib.ptr(ep1), 4, None))
-    assert int(ep1[0]) - int(ep0[0]) == frames * 498, "the persistent frame decoder did not run every sampled frame"
+        return codes_per_utterance(model, [prompt], frames, smp, seeds=[seed])[0]
+    ref, got = ab(model, "dec_frame", run, frames * handoffs("dec_frame", args.n_audio_codebooks))
     assert len(got) == frames and first_divergence(got, ref) is None, \
         f"sampled dec_frame codes differ from the launch path at {first_divergence(got, ref)}"
     assert np.array_equal(run(), got)                                     # deterministic per seed
@@ -106,38 +70,29 @@ def test_dec_frame_sampled_matches_launch_path_and_oracle(top_k, dtype):
     del model
 
 
-
-
 def test_dec_frame_top_k_1_equals_greedy():
     """Temperature 0.8 with top_k = 1 keeps the maximum alone, whatever the noise: the radix select runs all
     four passes with one key left to find, and the Gumbel pass and the block arg-max see one candidate.  B = 1
     bf16 on the persistent frame decoder, 4 frames: codes equal to the same engine's greedy codes and to the
     oracle's.  No head of these frames has its two largest logits equal (asserted on the oracle's logits), so
     a threshold off by one entry cannot hide behind a tie."""
-    from csm_mlx import _lib
-    from csm_mlx.generation import generate_codes_batch
-    from csm_mlx.models import CSM
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype="bf16")
-    model.load_weights(w)
-    L = _lib.lib()
+    args, w, model = build_model("1b", "bf16")
     prompt, frames = tokenize_text_segment(prompt_ids(31), 0, 32), 4
     orc, logs = oracle_for(args, w, bf16=True).generate_codes(*prompt, frames, collect_logits=True)
     for c0, ci in logs:
         for row in (c0, *ci):
             top = np.sort(row)[-2:]
             assert top[1] > top[0], "two equal maxima: pick another prompt"
-    _lib.check(L.csm_set_option(model.engine, b"dec_frame", 1))
+    set_option(model, "dec_frame", 1)
 
     def run(smp):
-        ep0, ep1 = np.zeros(1, np.uint32), np.zeros(1, np.uint32)
-        _lib.check(L.csm_debug_read(model.engine, b"dec_frame_epoch", _lib.ptr(ep0), 4, None))
-        h, n, _ = generate_codes_batch(model, [prompt], frames, sampler=smp, seeds=[777])
-        _lib.check(L.csm_debug_read(model.engine, b"dec_frame_epoch", _lib.ptr(ep1), 4, None))
-        assert int(ep1[0]) - int(ep0[0]) == frames * 498, "the persistent frame decoder did not run every frame"
-        return h[: n[0], 0].copy()
+        e0 = epoch(model, "dec_frame")
+        got = codes_per_utterance(model, [prompt], frames, smp, seeds=[777])[0]
+        assert epoch(model, "dec_frame") - e0 == frames * handoffs("dec_frame", args.n_audio_codebooks), \
+            "the persistent frame decoder did not run every frame"
+        return got
     greedy, got = run(Sampler(0.0, 0)), run(Sampler(0.8, 1))
     del model
     assert len(got) == frames and first_divergence(got, greedy) is None, \

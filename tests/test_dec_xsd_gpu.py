@@ -10,55 +10,29 @@ deterministic run to run, and leave no hand-off timeout behind (generation.py:72
 import numpy as np
 import pytest
 
-from helpers import csm_weights, first_divergence, oracle_batch, oracle_for, prompt_ids
+from helpers import first_divergence, oracle_batch, oracle_for, prompt_ids
+from rigs import ab, build_model, epoch, frame_taps, handoffs, set_option, synchronize
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def model_1b():
-    from csm_mlx.models import CSM
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype="bf16", max_batch=32)
-    model.load_weights(w)
+    args, w, model = build_model("1b", "bf16", max_batch=32)
     yield args, w, model
     del model
 
 
-def _epoch(model):
-    from csm_mlx import _lib
-    ep = np.zeros(1, np.uint32)
-    _lib.check(_lib.lib().csm_debug_read(model.engine, b"dec_xsd_epoch", _lib.ptr(ep), 4, None))
-    return int(ep[0])
-
-
 def _run(model, prompts, frames, sampler):
-    from csm_mlx.generation import FrameCache
-    K, V = model.n_audio_codebooks, model.n_audio_vocab
-    Vp = (V + 7) // 8 * 8
-    B = len(prompts)
-    cache = FrameCache(model, B, sampler, [1234 + b for b in range(B)])
-    for b, (t, m) in enumerate(prompts):
-        cache.prefill(b, t, m)
-    logs = []
-    for _ in range(frames):
-        cache.run(1)
-        logs.append(cache.debug("ci_logits", (K - 1, B, Vp))[:, :, :V])
-    hist, n, _ = cache.codes()
-    return hist, n, logs
+    """(hist, n, ci logits (F, B, K-1, V))."""
+    hist, n, taps = frame_taps(model, prompts, frames, sampler, [1234 + b for b in range(len(prompts))], ("ci_logits",))
+    return hist, n, taps["ci_logits"]
 
 
 def _ab(model, prompts, frames, sampler):
-    from csm_mlx import _lib
-    L = _lib.lib()
-    _lib.check(L.csm_set_option(model.engine, b"dec_xsd", 0))
-    ref = _run(model, prompts, frames, sampler)
-    _lib.check(L.csm_set_option(model.engine, b"dec_xsd", 1))
-    e0 = _epoch(model)
-    got = _run(model, prompts, frames, sampler)
-    K = model.n_audio_codebooks
-    assert _epoch(model) - e0 == frames * (K - 2), "the persistent step did not run every codebook step >= 2"
-    _lib.check(L.csm_synchronize(model.engine))
+    ref, got = ab(model, "dec_xsd", lambda: _run(model, prompts, frames, sampler),
+                  frames * handoffs("dec_xsd", model.n_audio_codebooks))
+    synchronize(model)
     return ref, got
 
 
@@ -118,10 +92,7 @@ def test_dec_xsd_sampled_matches_launch_path(model_1b):
 
 @pytest.fixture(scope="module")
 def model_1b_q4():
-    from csm_mlx.models import CSM
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype="q4", max_batch=64)
-    model.load_weights(w)
+    args, w, model = build_model("1b", "q4", max_batch=64)
     yield args, w, model
     del model
 
@@ -159,14 +130,13 @@ def test_dec_xsd_timeout_reported_and_recovered(model_1b):
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
     args, w, model = model_1b
-    L = _lib.lib()
     B = 16
     prompts = [tokenize_text_segment(prompt_ids(900 + b, 10 + b % 3), 0, args.n_audio_codebooks) for b in range(B)]
-    _lib.check(L.csm_set_option(model.engine, b"dec_xsd", 1))
-    _lib.check(L.csm_set_option(model.engine, b"inject_handoff_error", 1))
+    set_option(model, "dec_xsd", 1)
+    set_option(model, "inject_handoff_error", 1)
     with pytest.raises(_lib.CsmHipError, match="hand-off wait timed out"):
         _run(model, prompts, 2, Sampler(0.0, 0))
-    _lib.check(L.csm_synchronize(model.engine))
+    synchronize(model)
     (rh, rn, _), (gh, gn, _) = _ab(model, prompts, 3, Sampler(0.0, 0))
     assert np.array_equal(rn, gn)
     for b in range(B):
@@ -178,18 +148,16 @@ def test_dec_xsd_in_launch_sampler_matches_sample_kernel(model_1b_q4, B):
     """Sampled steps (temperature 0.8, top-k 50) with the sampler inside the step's launch (role_s: the
     radix-select threshold and Gumbel-max of sample_kernel on 512 threads) against the same kernel with
     sample_kernel launched after it (option dec_xsd_sample 0): 4 frames of int4 rows, codes identical."""
-    from csm_mlx import _lib
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
     args, w, model = model_1b_q4
-    L = _lib.lib()
     prompts = [tokenize_text_segment(prompt_ids(950 + b, 10 + b % 3), 0, args.n_audio_codebooks) for b in range(B)]
-    _lib.check(L.csm_set_option(model.engine, b"dec_xsd", 1))
-    _lib.check(L.csm_set_option(model.engine, b"dec_xsd_sample", 0))
+    set_option(model, "dec_xsd", 1)
+    set_option(model, "dec_xsd_sample", 0)
     ref = _run(model, prompts, 4, Sampler(0.8, 50))
-    _lib.check(L.csm_set_option(model.engine, b"dec_xsd_sample", 1))
+    set_option(model, "dec_xsd_sample", 1)
     got = _run(model, prompts, 4, Sampler(0.8, 50))
-    _lib.check(L.csm_synchronize(model.engine))
+    synchronize(model)
     assert np.array_equal(ref[1], got[1])
     for b in range(B):
         d = first_divergence(got[0][: got[1][b], b], ref[0][: ref[1][b], b])
@@ -201,11 +169,9 @@ def test_dec_xsd_in_launch_sampler_top_k_1_equals_greedy(model_1b_q4):
     is kept whatever the noise, so the radix select runs all four passes with one key left to find.  B = 8
     int4 rows, 4 frames: codes equal to the same engine's greedy codes and to the oracle's.  No head of these
     rows and frames has its two largest logits equal (asserted on the oracle's logits)."""
-    from csm_mlx import _lib
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
     args, w, model = model_1b_q4
-    L = _lib.lib()
     B, frames = 8, 4
     prompts = [tokenize_text_segment(prompt_ids(800 + b, 10 + b % 3), 0, args.n_audio_codebooks) for b in range(B)]
     ref = oracle_batch(oracle_for(args, w, q4=True), prompts, frames, collect_logits=True)
@@ -215,17 +181,17 @@ def test_dec_xsd_in_launch_sampler_top_k_1_equals_greedy(model_1b_q4):
             for row in (c0, *ci):
                 top = np.sort(row)[-2:]
                 assert top[1] > top[0], "two equal maxima: pick other prompts"
-    _lib.check(L.csm_set_option(model.engine, b"dec_xsd", 1))
-    _lib.check(L.csm_set_option(model.engine, b"dec_xsd_sample", 1))
-    K = model.n_audio_codebooks
+    set_option(model, "dec_xsd", 1)
+    set_option(model, "dec_xsd_sample", 1)
 
     def run(smp):
-        e0 = _epoch(model)
+        e0 = epoch(model, "dec_xsd")
         h, n, _ = _run(model, prompts, frames, smp)
-        assert _epoch(model) - e0 == frames * (K - 2), "the persistent step did not run every codebook step >= 2"
+        assert epoch(model, "dec_xsd") - e0 == frames * handoffs("dec_xsd", model.n_audio_codebooks), \
+            "the persistent step did not run every codebook step >= 2"
         return h, n
     (gh, gn), (sh, sn) = run(Sampler(0.0, 0)), run(Sampler(0.8, 1))
-    _lib.check(L.csm_synchronize(model.engine))
+    synchronize(model)
     for b in range(B):
         assert gn[b] == frames and sn[b] == frames
         d = first_divergence(sh[:frames, b], gh[:frames, b])

@@ -1,17 +1,10 @@
 """Multi-process path of bench.py on CPU: world_size 2 over gloo (the GPU run uses RCCL)."""
 import os
-import socket
 
 import pytest
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from helpers import free_port as _free_port
 
 
 def _worker(rank, world, port, q):

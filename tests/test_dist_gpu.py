@@ -15,23 +15,16 @@
   is the largest RCCL group this one-GPU box can hold.  (The 8-GPU RCCL run is the driver's.)"""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from helpers import free_port as _free_port
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _bench(tmp_path, nproc, batch_per_rank, frames, name, backend="gloo", launcher=False, model="tiny",

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 from helpers import BAR_MARGIN, TAPS, csm_weights, f64_reference, prompt_ids, tap_errors, tiny_prompt_ids
+from rigs import TAP_NAMES, build_model, epoch, frame_taps, handoffs, set_option, synchronize
 
 pytestmark = pytest.mark.gpu
 
@@ -30,11 +31,7 @@ EPOCHS = ("dec_frame_epoch", "dec_xsd_epoch", "bb_step_epoch")
 
 
 def _engine(key, dtype, max_batch):
-    from csm_mlx.models import CSM
-    args, w = _weights(key)
-    model = CSM(args, dtype=dtype, max_batch=max_batch)
-    model.load_weights(w)
-    return args, w, model
+    return build_model(_weights(key), dtype, max_batch)
 
 
 _W = {}
@@ -66,40 +63,22 @@ def engine_1b_q4():
 
 
 def _epochs(model):
-    from csm_mlx import _lib
-    out = {}
-    for name in EPOCHS:
-        ep = np.zeros(1, np.uint32)
-        _lib.check(_lib.lib().csm_debug_read(model.engine, name.encode(), _lib.ptr(ep), 4, None))
-        out[name] = int(ep[0])
-    return out
+    return {name: epoch(model, name[:-len("_epoch")]) for name in EPOCHS}
 
 
 def _run(model, prompts, forced=None):
     """2 frames, one at a time; returns codes (F, B, K) and the taps (h_last (F, B, D), c0 (F, B, V),
     ci (F, B, K-1, V)).  forced (F, B, K): the frames are csm_frame_forced on these codes."""
     from csm_mlx import _lib
-    from csm_mlx.generation import FrameCache
     from csm_mlx.sampling import Sampler
-    K, V, D = model.n_audio_codebooks, model.n_audio_vocab, model.n_backbone_embedding
-    Vp = (V + 7) // 8 * 8
-    B = len(prompts)
-    cache = FrameCache(model, B, Sampler(0.0, 0), [0] * B)
-    for b, (t, m) in enumerate(prompts):
-        cache.prefill(b, t, m)
-    h, c0, ci = [], [], []
-    for f in range(FRAMES):
-        if forced is None:
-            cache.run(1)
-        else:
-            codes = np.ascontiguousarray(forced[f], np.int32)
-            _lib.check(_lib.lib().csm_frame_forced(model.engine, _lib.ptr(codes), None, None, None))
-        h.append(cache.debug("h_last", (B, D)))
-        c0.append(cache.debug("c0_logits", (B, Vp))[:, :V])
-        ci.append(cache.debug("ci_logits", (K - 1, B, Vp))[:, :, :V].transpose(1, 0, 2))
-    hist, n, _ = cache.codes()
+
+    def force(cache, f):
+        codes = np.ascontiguousarray(forced[f], np.int32)
+        _lib.check(_lib.lib().csm_frame_forced(model.engine, _lib.ptr(codes), None, None, None))
+    hist, n, taps = frame_taps(model, prompts, FRAMES, Sampler(0.0, 0), [0] * len(prompts), TAP_NAMES,
+                               step=None if forced is None else force)
     assert hist.shape[0] == FRAMES and (n == FRAMES).all(), "an utterance ended inside the window"
-    return hist.copy(), (np.stack(h), np.stack(c0), np.stack(ci))
+    return hist, tuple(taps[t] for t in TAP_NAMES)
 
 
 _REFS = {}
@@ -118,21 +97,19 @@ def _reference(key, dtype, prompts, codes):
 def _check(key, dtype, model, prompts, options=(), forced=None, expect=None, capsys=None):
     """Run the case with ``options`` (name -> 0) switched off, compare every tap with the float64 oracle
     forced on the engine's codes, hold the epoch deltas to ``expect``."""
-    from csm_mlx import _lib
-    L = _lib.lib()
     for name in options:
-        _lib.check(L.csm_set_option(model.engine, name.encode(), 0))
+        set_option(model, name, 0)
     try:
         e0 = _epochs(model) if expect is not None else None
         codes, got = _run(model, prompts, forced)
-        _lib.check(L.csm_synchronize(model.engine))                          # no hand-off timeout left behind
+        synchronize(model)                                                   # no hand-off timeout left behind
         if expect is not None:
             e1 = _epochs(model)
             delta = {n: e1[n] - e0[n] for n in EPOCHS}
             assert delta == expect, f"kernels that ran (epoch deltas) {delta}, expected {expect}"
     finally:
         for name in options:
-            _lib.check(L.csm_set_option(model.engine, name.encode(), 1))
+            set_option(model, name, 1)
     if forced is not None:
         assert np.array_equal(codes, forced), "the forced codes are not the frame's codes"
     else:                                                                    # first-index arg-max of its own logits
@@ -162,8 +139,9 @@ def _prompts_1b(B):
 
 
 def _expect(K, B, dec_frame=False, dec_xsd=False, bb_step=False):
-    return {"dec_frame_epoch": 498 * FRAMES if dec_frame else 0, "dec_xsd_epoch": (K - 2) * FRAMES if dec_xsd else 0,
-            "bb_step_epoch": 80 * (FRAMES - 1) * B if bb_step else 0}
+    return {"dec_frame_epoch": handoffs("dec_frame", K) * FRAMES if dec_frame else 0,
+            "dec_xsd_epoch": handoffs("dec_xsd", K) * FRAMES if dec_xsd else 0,
+            "bb_step_epoch": handoffs("bb_step", K) * (FRAMES - 1) * B if bb_step else 0}
 
 
 # ----------------------------------------------------------------------------- csm_1b, batch 1

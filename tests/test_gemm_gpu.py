@@ -11,36 +11,24 @@ import numpy as np
 import pytest
 
 from helpers import csm_weights, first_divergence, oracle_batch, oracle_for, prompt_ids, tiny_prompt_ids
+from rigs import build_model, frame_taps, set_option
 
 pytestmark = pytest.mark.gpu
 
 
 def _model(args, weights, dtype, max_batch):
-    from csm_mlx.models import CSM
-    m = CSM(args, dtype=dtype, max_batch=max_batch)
-    m.load_weights(weights)
-    return m
+    return build_model((args, weights), dtype, max_batch)[2]
 
 
 def _batch_vs_oracle(args, w, id_sets, frames, rtol, dtype="bf16", logits_of=None):
     """logits_of: utterances whose logits are compared every frame (codes: all of them)."""
-    from csm_mlx.generation import FrameCache
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
-    K, V = args.n_audio_codebooks, args.n_audio_vocab
-    Vp = (V + 7) // 8 * 8
     B = len(id_sets)
     model = _model(args, w, dtype, B)
     o = oracle_for(args, w, bf16=(dtype == "bf16"), q4=(dtype == "q4"))
-    prompts = [tokenize_text_segment(ids, 0, K) for ids in id_sets]
-    cache = FrameCache(model, B, Sampler(0.0, 0), [0] * B)
-    for b, (t, m) in enumerate(prompts):
-        cache.prefill(b, t, m)
-    logs = []
-    for _ in range(frames):
-        cache.run(1)
-        logs.append((cache.debug("c0_logits", (B, Vp))[:, :V], cache.debug("ci_logits", (K - 1, B, Vp))[:, :, :V]))
-    hist, n, _ = cache.codes()
+    prompts = [tokenize_text_segment(ids, 0, args.n_audio_codebooks) for ids in id_sets]
+    hist, n, taps = frame_taps(model, prompts, frames, Sampler(0.0, 0), [0] * B, ("c0_logits", "ci_logits"))
     del model
     ref = oracle_batch(o, prompts, frames, collect_logits=True)
     bad = []
@@ -54,7 +42,7 @@ def _batch_vs_oracle(args, w, id_sets, frames, rtol, dtype="bf16", logits_of=Non
         if logits_of is not None and b not in logits_of:
             continue
         for f in range(len(ref_codes)):
-            for got, want in ((logs[f][0][b], ref_logs[f][0]), (logs[f][1][:, b], ref_logs[f][1])):
+            for got, want in ((taps["c0_logits"][f, b], ref_logs[f][0]), (taps["ci_logits"][f, b], ref_logs[f][1])):
                 err = np.abs(got - want).max()
                 assert err <= rtol * np.abs(want).max(), f"utterance {b} frame {f}: logits err {err:.3e}"
     assert not bad, "; ".join(bad)
@@ -115,30 +103,17 @@ def test_csm_1b_q4_batched_mfma(B):
 def test_batched_prefill_matches_per_utterance(dtype):
     """csm_prefill_batch (every prompt's rows in one pass per projection, ragged lengths) against
     csm_prefill per utterance: identical greedy codes, logits within fp32 summation-order noise."""
-    from csm_mlx.generation import FrameCache
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
     args, w = csm_weights("tiny")
-    K, V = args.n_audio_codebooks, args.n_audio_vocab
-    Vp = (V + 7) // 8 * 8
     B = 12
-    prompts = [tokenize_text_segment(tiny_prompt_ids(300 + b, 2 + (5 * b) % 11), 0, K) for b in range(B)]
+    prompts = [tokenize_text_segment(tiny_prompt_ids(300 + b, 2 + (5 * b) % 11), 0, args.n_audio_codebooks) for b in range(B)]
     out = []
     for batched in (False, True):
         model = _model(args, w, dtype, B)
-        cache = FrameCache(model, B, Sampler(0.0, 0), [0] * B)
-        if batched:
-            cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(prompts)])
-        else:
-            for b, (t, m) in enumerate(prompts):
-                cache.prefill(b, t, m)
-        logs = []
-        for _ in range(4):
-            cache.run(1)
-            logs.append(cache.debug("c0_logits", (B, Vp))[:, :V].copy())
-        hist, n, _ = cache.codes()
-        out.append((hist.copy(), n.copy(), logs))
-        del cache, model
+        hist, n, taps = frame_taps(model, prompts, 4, Sampler(0.0, 0), [0] * B, ("c0_logits",), prefill_batch=batched)
+        out.append((hist, n, taps["c0_logits"]))
+        del model
     (h0, n0, l0), (h1, n1, l1) = out
     assert np.array_equal(n0, n1) and np.array_equal(h0, h1)
     for a, b in zip(l0, l1):
@@ -151,30 +126,18 @@ def test_csm_1b_bf16_batch_composition_invariance():
     as utterance 5 of a B = 32 batch prefilled in one csm_prefill_batch pass (matrix-core GEMMs whose
     split-K slice count follows the batch's total row count) -- 6 frames, codes identical, c0 logits
     within the bf16 bar.  (Summation order differs between the two; greedy codes are the bar.)"""
-    from csm_mlx.generation import FrameCache
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
     args, w = csm_weights("1b")
-    K, V = args.n_audio_codebooks, args.n_audio_vocab
-    Vp = (V + 7) // 8 * 8
     B, frames, j = 32, 6, 5
-    prompts = [tokenize_text_segment(prompt_ids(700 + b, 8 + b % 5), 0, K) for b in range(B)]
+    prompts = [tokenize_text_segment(prompt_ids(700 + b, 8 + b % 5), 0, args.n_audio_codebooks) for b in range(B)]
     model = _model(args, w, "bf16", B)
     out = []
     for batch in ([prompts[j]], prompts):
-        cache = FrameCache(model, len(batch), Sampler(0.0, 0), [0] * len(batch))
-        if len(batch) > 1:
-            cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(batch)])
-        else:
-            cache.prefill(0, *batch[0])
-        logs = []
-        for _ in range(frames):
-            cache.run(1)
-            logs.append(cache.debug("c0_logits", (len(batch), Vp))[:, :V].copy())
-        hist, n, _ = cache.codes()
+        hist, n, taps = frame_taps(model, batch, frames, Sampler(0.0, 0), [0] * len(batch), ("c0_logits",),
+                                   prefill_batch=len(batch) > 1)
         b = 0 if len(batch) == 1 else j
-        out.append((hist[: n[b], b].copy(), [l[b] for l in logs]))
-        del cache
+        out.append((hist[: n[b], b].copy(), taps["c0_logits"][:, b]))
     del model
     (c1, l1), (c32, l32) = out
     assert len(c1) == frames and first_divergence(c1, c32) is None, "codes depend on the batch composition"
@@ -189,31 +152,19 @@ def test_streaming_decoder_matches_wide_gemm(B, dtype, bb):
     gemm_wide_kernel: identical greedy codes, ci logits within fp32 summation-order noise (both sum
     exact fp32 products), 4 frames, csm_1b bf16 and int4; bb=1 also runs the backbone's projections
     on it (option bb_xs, on by default since round 4; bb=0 keeps it on gemm_wide)."""
-    from csm_mlx import _lib
-    from csm_mlx.generation import FrameCache
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
     args, w = csm_weights("1b")
-    K, V = args.n_audio_codebooks, args.n_audio_vocab
-    Vp = (V + 7) // 8 * 8
-    prompts = [tokenize_text_segment(prompt_ids(900 + b, 9 + b % 4), 0, K) for b in range(B)]
+    prompts = [tokenize_text_segment(prompt_ids(900 + b, 9 + b % 4), 0, args.n_audio_codebooks) for b in range(B)]
     model = _model(args, w, dtype, B)
-    L = _lib.lib()
     out = []
     for on in (0, 1):
-        _lib.check(L.csm_set_option(model.engine, b"gemm_xs", on))
-        _lib.check(L.csm_set_option(model.engine, b"bb_xs", on * bb))
-        cache = FrameCache(model, B, Sampler(0.0, 0), [0] * B)
-        cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(prompts)])
-        logs = []
-        for _ in range(4):
-            cache.run(1)
-            logs.append(cache.debug("ci_logits", (K - 1, B, Vp))[:, :, :V].copy())
-        hist, n, _ = cache.codes()
-        out.append((hist.copy(), n.copy(), logs))
-        del cache
-    _lib.check(L.csm_set_option(model.engine, b"gemm_xs", 1))
-    _lib.check(L.csm_set_option(model.engine, b"bb_xs", 1))
+        set_option(model, "gemm_xs", on)
+        set_option(model, "bb_xs", on * bb)
+        hist, n, taps = frame_taps(model, prompts, 4, Sampler(0.0, 0), [0] * B, ("ci_logits",), prefill_batch=True)
+        out.append((hist, n, taps["ci_logits"]))
+    set_option(model, "gemm_xs", 1)
+    set_option(model, "bb_xs", 1)
     del model
     (h0, n0, l0), (h1, n1, l1) = out
     assert np.array_equal(n0, n1) and np.array_equal(h0, h1), "streaming decoder codes differ from gemm_wide"

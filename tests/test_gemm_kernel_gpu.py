@@ -12,6 +12,8 @@ import ctypes
 import numpy as np
 import pytest
 
+from rigs import set_option
+
 pytestmark = pytest.mark.gpu
 
 NAMES = ["backbone.layers.0.self_attn.q_proj.weight", "backbone.layers.3.self_attn.v_proj.weight",
@@ -30,7 +32,7 @@ def _model(dtype):
 def _linear(model, name, x, mfma):
     from csm_mlx import _lib
     L = _lib.lib()
-    _lib.check(L.csm_set_option(model.engine, b"linear_mfma", int(mfma)))
+    set_option(model, "linear_mfma", mfma)
     n_out = _out_width(model, name)
     y = np.zeros((x.shape[0], n_out), np.float32)
     _lib.check(L.csm_linear(model.engine, name.encode(), x.shape[0], _lib.ptr(x), _lib.ptr(y)))

@@ -5,7 +5,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import csm_weights, first_divergence, oracle_for
+from helpers import first_divergence, oracle_for
+from rigs import build_model
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -15,13 +16,10 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 def stack():
     from csm_mlx.config import MIMI_CONFIGURATION
     from csm_mlx.mimi import MimiCodec
-    from csm_mlx.models import CSM
     from csm_mlx.tokenizers import set_audio_tokenizer
     from csm_mlx.weights import synthetic_mimi_weights
     from oracle.mimi_oracle import OracleMimi
-    args, w = csm_weights("tiny")
-    model = CSM(args, dtype="float32")
-    model.load_weights(w)
+    args, w, model = build_model("tiny", "float32")
     mm = MIMI_CONFIGURATION["tiny"]
     mw = synthetic_mimi_weights(mm)
     codec = MimiCodec(mm, max_batch=4, max_frames=300)

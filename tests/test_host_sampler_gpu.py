@@ -7,7 +7,8 @@ graph path, bit for bit."""
 import numpy as np
 import pytest
 
-from helpers import csm_weights, first_divergence, oracle_for, prompt_ids, tiny_prompt_ids
+from helpers import first_divergence, oracle_for, prompt_ids, tiny_prompt_ids
+from rigs import build_model, codes_per_utterance
 
 pytestmark = pytest.mark.gpu
 
@@ -23,17 +24,13 @@ def argmax_sampler(logits):
 
 
 def _gpu_codes(model, prompts, frames, sampler):
-    from csm_mlx.generation import generate_codes_batch, _resolve_sampler
-    hist, n, _ = generate_codes_batch(model, prompts, frames, sampler=_resolve_sampler(0.8, sampler))
-    return [hist[: n[b], b].copy() for b in range(len(prompts))]
+    from csm_mlx.generation import _resolve_sampler
+    return codes_per_utterance(model, prompts, frames, _resolve_sampler(0.8, sampler))
 
 
 def test_host_sampler_matches_oracle_tiny():
-    from csm_mlx.models import CSM
     from csm_mlx.tokenizers import tokenize_text_segment
-    args, w = csm_weights("tiny")
-    model = CSM(args, dtype="float32", max_batch=2)
-    model.load_weights(w)
+    args, w, model = build_model("tiny", "float32", max_batch=2)
     K = args.n_audio_codebooks
     ids = [tiny_prompt_ids(70 + b, 3 + b) for b in range(2)]
     prompts = [tokenize_text_segment(i, 0, K) for i in ids]
@@ -47,12 +44,9 @@ def test_host_sampler_matches_oracle_tiny():
 @pytest.mark.parametrize("which,dtype,B", [("tiny", "float32", 2), ("1b", "bf16", 1)])
 def test_host_argmax_sampler_equals_greedy_graph(which, dtype, B):
     """An arg-max callable on the host picks exactly what the GPU greedy path picks (first max)."""
-    from csm_mlx.models import CSM
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
-    args, w = csm_weights(which)
-    model = CSM(args, dtype=dtype, max_batch=B)
-    model.load_weights(w)
+    args, w, model = build_model(which, dtype, max_batch=B)
     K = args.n_audio_codebooks
     ids = [tiny_prompt_ids(90 + b, 4) if which == "tiny" else prompt_ids(90 + b) for b in range(B)]
     prompts = [tokenize_text_segment(i, 0, K) for i in ids]
@@ -67,14 +61,11 @@ def test_host_argmax_sampler_equals_greedy_graph(which, dtype, B):
 def test_stream_generate_with_host_sampler():
     """stream_generate(sampler=callable) streams the host-sampled frames through decode_step."""
     from csm_mlx.generation import stream_generate
-    from csm_mlx.models import CSM
     from csm_mlx.tokenizers import set_audio_tokenizer
     from csm_mlx.config import MIMI_CONFIGURATION
     from csm_mlx.mimi import MimiCodec
     from csm_mlx.weights import synthetic_mimi_weights
-    args, w = csm_weights("tiny")
-    model = CSM(args, dtype="float32", max_batch=1)
-    model.load_weights(w)
+    args, w, model = build_model("tiny", "float32", max_batch=1)
     mc = MIMI_CONFIGURATION["tiny"]
     codec = MimiCodec(mc, max_batch=2)
     codec.load_weights(synthetic_mimi_weights(mc, 0))

@@ -7,7 +7,8 @@ import re
 import numpy as np
 import pytest
 
-from helpers import csm_weights, oracle_for, tiny_prompt_ids
+from helpers import oracle_for, tiny_prompt_ids
+from rigs import build_model
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,14 +29,11 @@ def test_stub_text_exposes_reference_calls():
 
 def test_integration_stub_runs_verbatim(monkeypatch):
     from csm_mlx import _lib
-    from csm_mlx.models import CSM
     from oracle.csm_oracle import text_frame
     monkeypatch.setenv("CSM_HIP_LIB", _lib.LIB_PATH)
     ns = {}
     exec(compile(_stub_source(), "INTEGRATION.md:stub", "exec"), ns)
-    args, w = csm_weights("tiny")
-    model = CSM(args, dtype="float32")
-    model.load_weights(w)
+    args, w, model = build_model("tiny", "float32")
     engine = model.engine
     K = args.n_audio_codebooks
     ids = tiny_prompt_ids(5)

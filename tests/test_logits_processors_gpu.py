@@ -11,7 +11,8 @@ window penalised once (twice: 3.1 < 10), frame 6 = B that B has left the window;
 import numpy as np
 import pytest
 
-from helpers import csm_weights, first_divergence, oracle_for, prompt_ids, tiny_prompt_ids
+from helpers import first_divergence, oracle_for, prompt_ids, tiny_prompt_ids
+from rigs import ab, build_model, codes_per_utterance, frame_taps, handoffs, synchronize
 
 pytestmark = pytest.mark.gpu
 
@@ -47,35 +48,17 @@ def wrapped(procs, raw=None):
 def run_frames(model, prompts, frames, sampler, seeds, procs):
     """Frame by frame (one graph replay or one paused frame per call): codes (F, B, K) and the c0_logits
     tap (B, V) after every frame."""
-    from csm_mlx.generation import FrameCache, device_processors
-    V = model.n_audio_vocab
-    Vp = (V + 7) // 8 * 8
+    from csm_mlx.generation import device_processors
     dev = device_processors(procs, sampler)
-    cache = FrameCache(model, len(prompts), sampler, seeds, dev)
-    for b, (t, m) in enumerate(prompts):
-        cache.prefill(b, t, m)
-    taps, hist = [], []
-    for _ in range(frames):
-        if dev is not None or not procs:
-            cache.run(1)
-        else:
-            cache.run_processed(procs, hist)
-        taps.append(cache.debug("c0_logits", (len(prompts), Vp))[:, :V].copy())
-    return cache.codes()[0], taps
-
-
-def batch_codes(model, prompts, frames, sampler, seeds, procs):
-    from csm_mlx.generation import generate_codes_batch
-    hist, n, _ = generate_codes_batch(model, prompts, frames, sampler=sampler, seeds=seeds, logits_processors=procs)
-    return [hist[: n[b], b] for b in range(len(prompts))]
+    c0_hist = []
+    paused = None if dev is not None or not procs else lambda cache, f: cache.run_processed(procs, c0_hist)
+    hist, _, taps = frame_taps(model, prompts, frames, sampler, seeds, ("c0_logits",), step=paused, processors=dev)
+    return hist, taps["c0_logits"]
 
 
 @pytest.fixture(scope="module")
 def tiny():
-    from csm_mlx.models import CSM
-    args, w = csm_weights("tiny")
-    m = CSM(args, dtype="float32", max_batch=4)
-    m.load_weights(w)
+    args, w, m = build_model("tiny", "float32", max_batch=4)
     return m, oracle_for(args, w), args
 
 
@@ -93,11 +76,11 @@ def test_launch_path_greedy_bias_and_penalty(tiny, context, frames):
     K, seeds, smp = args.n_audio_codebooks, (21, 22, 23), Sampler(0.0, 0)
     prompts, procs = tiny_prompts(args, seeds), procs_ab(context)
     assert device_processors(procs, smp) is not None
-    got = batch_codes(model, prompts, frames, smp, None, procs)
+    got = codes_per_utterance(model, prompts, frames, smp, None, procs)
     raw = []
     host = wrapped(procs, raw)
     assert device_processors(host, smp) is None
-    paused = batch_codes(model, prompts, frames, smp, None, host)
+    paused = codes_per_utterance(model, prompts, frames, smp, None, host)
     print("max |raw c0 logit|", max(float(np.abs(r).max()) for r in raw))
     assert len(raw) == frames and all(np.abs(r).max() < RAW_BOUND for r in raw)
     for b, s in enumerate(seeds):
@@ -128,10 +111,10 @@ def test_launch_path_sampled_penalty(tiny, sampler_kw, seeds):
     prompts = tiny_prompts(args, seeds)
     rng = [1000 + s for s in seeds]
     procs = make_logits_processors(repetition_penalty=1.3, repetition_context_size=20)
-    got = batch_codes(model, prompts, frames, smp, rng, procs)
+    got = codes_per_utterance(model, prompts, frames, smp, rng, procs)
     raw = []
-    paused = batch_codes(model, prompts, frames, smp, rng, wrapped(procs, raw))
-    plain = batch_codes(model, prompts, frames, smp, rng, None)
+    paused = codes_per_utterance(model, prompts, frames, smp, rng, wrapped(procs, raw))
+    plain = codes_per_utterance(model, prompts, frames, smp, rng, None)
     negative = 0
     for b, s in enumerate(seeds):
         ref = o.generate_codes(*text_frame(tiny_prompt_ids(s), K), frames, temperature=smp.temp, top_k=smp.top_k,
@@ -146,24 +129,9 @@ def test_launch_path_sampled_penalty(tiny, sampler_kw, seeds):
 
 @pytest.fixture(scope="module", params=["bf16", "q4"])
 def model_1b(request):
-    from csm_mlx.models import CSM
-    args, w = csm_weights("1b")
-    m = CSM(args, dtype=request.param, max_batch=8)
-    m.load_weights(w)
+    args, w, m = build_model("1b", request.param, max_batch=8)
     yield m, args, w, request.param
     del m
-
-
-def _epoch(model):
-    from csm_mlx import _lib
-    ep = np.zeros(1, np.uint32)
-    _lib.check(_lib.lib().csm_debug_read(model.engine, b"dec_frame_epoch", _lib.ptr(ep), 4, None))
-    return int(ep[0])
-
-
-def _dec_frame(model, on):
-    from csm_mlx import _lib
-    _lib.check(_lib.lib().csm_set_option(model.engine, b"dec_frame", int(on)))
 
 
 def test_persistent_decoder_greedy(model_1b):
@@ -173,12 +141,8 @@ def test_persistent_decoder_greedy(model_1b):
     model, args, w, dtype = model_1b
     frames, smp, procs = 8, Sampler(0.0, 0), procs_ab(4)
     prompt = tokenize_text_segment(prompt_ids(41), 0, 32)
-    _dec_frame(model, 0)
-    ref, ref_taps = run_frames(model, [prompt], frames, smp, [0], procs)
-    _dec_frame(model, 1)
-    ep0 = _epoch(model)
-    got, got_taps = run_frames(model, [prompt], frames, smp, [0], procs)
-    assert _epoch(model) - ep0 == frames * 498, "the persistent frame decoder did not run every frame with processors on"
+    (ref, ref_taps), (got, got_taps) = ab(model, "dec_frame", lambda: run_frames(model, [prompt], frames, smp, [0], procs),
+                                          frames * handoffs("dec_frame", args.n_audio_codebooks))
     raw = []
     paused, _ = run_frames(model, [prompt], frames, smp, [0], wrapped(procs, raw))
     print("max |raw c0 logit|", max(float(np.abs(r).max()) for r in raw))
@@ -201,12 +165,8 @@ def test_persistent_decoder_sampled(model_1b, top_k):
     model, args, w, dtype = model_1b
     frames, smp, procs = 6, Sampler(0.8, top_k), procs_ab(4)
     prompt = tokenize_text_segment(prompt_ids(41), 0, 32)
-    _dec_frame(model, 0)
-    ref = batch_codes(model, [prompt], frames, smp, [4242], procs)[0]
-    _dec_frame(model, 1)
-    ep0 = _epoch(model)
-    got = batch_codes(model, [prompt], frames, smp, [4242], procs)[0]
-    assert _epoch(model) - ep0 == frames * 498
+    ref, got = ab(model, "dec_frame", lambda: codes_per_utterance(model, [prompt], frames, smp, [4242], procs)[0],
+                  frames * handoffs("dec_frame", args.n_audio_codebooks))
     assert len(got) == frames and first_divergence(got, ref) is None, \
         f"sampled codes differ from the launch path at frame {first_divergence(got, ref)}: {got[:, 0]} vs {ref[:, 0]}"
     assert set(got[:, 0]) <= {A, B_}
@@ -215,18 +175,17 @@ def test_persistent_decoder_sampled(model_1b, top_k):
 @pytest.mark.parametrize("model_1b", ["bf16"], indirect=True)
 def test_batched_1b_matches_paused_path(model_1b):
     """B = 8: the one-partial c0 hand-over into the batched step-1 projection and the persistent step."""
-    from csm_mlx import _lib
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
     model, args, w, dtype = model_1b
     frames, smp, procs = 6, Sampler(0.0, 0), procs_ab(4)
     prompts = [tokenize_text_segment(prompt_ids(50 + b), 0, 32) for b in range(8)]
-    got = batch_codes(model, prompts, frames, smp, None, procs)
-    paused = batch_codes(model, prompts, frames, smp, None, wrapped(procs))
+    got = codes_per_utterance(model, prompts, frames, smp, None, procs)
+    paused = codes_per_utterance(model, prompts, frames, smp, None, wrapped(procs))
     for b in range(8):
         assert first_divergence(got[b], paused[b]) is None, (b, got[b][:, 0], paused[b][:, 0])
         assert list(got[b][:, 0]) == expected_c0(frames, 4)
-    _lib.check(_lib.lib().csm_synchronize(model.engine))                          # no hand-off timeout flag left
+    synchronize(model)                                                            # no hand-off timeout flag left
 
 
 def test_stream_generate_and_graph_replay(tiny):
@@ -249,8 +208,8 @@ def test_stream_generate_and_graph_replay(tiny):
     for a, b in zip(dev, host):
         assert float(np.sqrt(np.mean((a - b) ** 2))) <= 1e-4
     prompts = tiny_prompts(args, (21, 22, 23))
-    one = batch_codes(model, prompts, 40, Sampler(0.0, 0), None, procs)
-    two = batch_codes(model, prompts, 40, Sampler(0.0, 0), None, procs)
+    one = codes_per_utterance(model, prompts, 40, Sampler(0.0, 0), None, procs)
+    two = codes_per_utterance(model, prompts, 40, Sampler(0.0, 0), None, procs)
     for a, b in zip(one, two):
         assert len(a) == 40 and np.array_equal(a, b)
         assert list(a[:, 0]) == expected_c0(40, 4)
@@ -263,7 +222,7 @@ def test_set_c0_processors_validation_and_reset(tiny):
     model, _, args = tiny
     V, L, smp = args.n_audio_vocab, _lib.lib(), Sampler(0.0, 0)
     prompts = tiny_prompts(args, (21,))
-    plain = batch_codes(model, prompts, 6, smp, None, None)[0]
+    plain = codes_per_utterance(model, prompts, 6, smp, None, None)[0]
     for bad in ((LogitBias((V,), (1.0,)), None), (LogitBias((-1,), (1.0,)), None), (None, RepetitionPenalty(-1.0, 4)),
                 (None, RepetitionPenalty(1.1, 257))):
         with pytest.raises(ValueError):
@@ -273,7 +232,7 @@ def test_set_c0_processors_validation_and_reset(tiny):
     for call in ((1, _lib.ptr(idx), _lib.ptr(val), 0.0, 0), (0, None, None, -1.0, 4), (0, None, None, 1.1, 257),
                  (0, None, None, 1.1, -1)):
         assert L.csm_set_c0_processors(model.engine, *call) == _lib.CSM_ERR_ARG
-    changed = batch_codes(model, prompts, 6, smp, None, procs_ab(4))[0]
+    changed = codes_per_utterance(model, prompts, 6, smp, None, procs_ab(4))[0]
     assert first_divergence(changed, plain) is not None
-    again = batch_codes(model, prompts, 6, smp, None, None)[0]                   # a new csm_begin: processors off
+    again = codes_per_utterance(model, prompts, 6, smp, None, None)[0]                   # a new csm_begin: processors off
     assert first_divergence(again, plain) is None

@@ -11,46 +11,25 @@
 
 Greedy codes bit-exact; logits within 2e-4 (fp32) / 2e-3 (bf16) x max|logit|; waveform <= 1e-4 RMS.
 """
-import os
-
 import numpy as np
 import pytest
 
 from helpers import csm_weights, first_divergence
+from rigs import build_model, fixture as _fixture, frame_taps
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _fixture(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
-
 
 def _model(args, w, dtype):
-    from csm_mlx.models import CSM
-    m = CSM(args, dtype=dtype, max_batch=1)
-    m.load_weights(w)
-    return m
+    return build_model((args, w), dtype, max_batch=1)[2]
 
 
 def _run_collect(model, tokens, mask, n_frames, keep, ci_cbs=None):
     """Frame loop (one graph replay per frame) with the logits of frames ``keep`` read back."""
-    from csm_mlx.generation import FrameCache
     from csm_mlx.sampling import Sampler
-    K, V = model.n_audio_codebooks, model.n_audio_vocab
-    Vp = (V + 7) // 8 * 8
-    cache = FrameCache(model, 1, Sampler(0.0, 0), [0])
-    cache.prefill(0, tokens, mask)
-    c0s, cis = [], []
-    for f in range(n_frames):
-        cache.run(1)
-        if f in keep:
-            c0s.append(cache.debug("c0_logits", (1, Vp))[0, :V])
-            ci = cache.debug("ci_logits", (K - 1, 1, Vp))[:, 0, :V]
-            cis.append(ci if ci_cbs is None else ci[[c - 1 for c in ci_cbs]])
-    hist, n, _ = cache.codes()
-    return hist[: n[0], 0], np.stack(c0s), np.stack(cis)
+    hist, n, taps = frame_taps(model, [(tokens, mask)], n_frames, Sampler(0.0, 0), [0], ("c0_logits", "ci_logits"), keep=keep)
+    ci = taps["ci_logits"][:, 0]
+    return hist[: n[0], 0], taps["c0_logits"][:, 0], ci if ci_cbs is None else ci[:, [c - 1 for c in ci_cbs]]
 
 
 def _check(codes, c0, ci, ref_codes, ref_c0, ref_ci, rtol):

@@ -21,7 +21,7 @@ import contextlib
 import numpy as np
 import pytest
 
-from helpers import MIMI_BAR_MARGIN, cut16, mimi_errors, mimi_pair
+from helpers import MIMI_BAR_MARGIN, cut16, mimi_errors, mimi_pair, rms as _rms
 
 CONFIGS = ["tiny", "mimi_202407"]
 # The two defects whose size the waveform sets, not the test: on these synthetic weights the old
@@ -31,10 +31,6 @@ CONFIGS = ["tiny", "mimi_202407"]
 # 7 taps of 1024 output channels) moves the 4-frame RMS to 1.2e-3 (mimi_202407) / 6.6e-5 (tiny).  Their bar side
 # is asserted like the others'; their RMS is printed, not asserted.
 RMS_SEES = ("last sample = its neighbour", "history sample zeroed")
-
-
-def _rms(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
 
 
 def _codes(m, frames=12):

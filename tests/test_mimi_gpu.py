@@ -4,36 +4,17 @@ Codes from encode must be bit-exact; decoded waveforms must agree within 1e-4 RM
 (the north-star tolerance) -- observed errors are ~1e-6.  Both transformer attention
 modes are covered ("mlx": moshi_mlx no-mask-in-call semantics, the default; "causal").
 """
-import dataclasses
-
 import numpy as np
 import pytest
+
+from helpers import mimi_pcm_clip as _pcm, rms as _rms
+from rigs import mimi_codec
 
 pytestmark = pytest.mark.gpu
 
 
-def _pcm(n, seed=0, amp=0.1):
-    t = np.arange(n) / 24000.0
-    rng = np.random.default_rng(seed)
-    f = rng.uniform(100, 400, 3)
-    x = amp * sum(np.sin(2 * np.pi * fi * t + rng.uniform(0, 6.28)) for fi in f) + rng.normal(0, 0.01, n)
-    return x.astype(np.float32)
-
-
 def _pair(name, mode, max_batch=2):
-    from csm_mlx.config import MIMI_CONFIGURATION
-    from csm_mlx.mimi import MimiCodec
-    from csm_mlx.weights import synthetic_mimi_weights
-    from oracle.mimi_oracle import OracleMimi
-    m = dataclasses.replace(MIMI_CONFIGURATION[name], attn_mode=mode)
-    w = synthetic_mimi_weights(m)
-    codec = MimiCodec(m, max_batch=max_batch, max_frames=200)
-    codec.load_weights(w)
-    return m, codec, OracleMimi(m, w)
-
-
-def _rms(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - b) ** 2)))
+    return mimi_codec(name, mode, max_batch, max_frames=200)
 
 
 @pytest.mark.parametrize("name", ["tiny", "mimi_202407"])

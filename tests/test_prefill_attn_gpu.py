@@ -13,7 +13,8 @@ attend to keys the first call cached.
 import numpy as np
 import pytest
 
-from helpers import csm_weights, first_divergence, oracle_batch, oracle_for, tiny_prompt_ids
+from helpers import first_divergence, oracle_batch, oracle_for, tiny_prompt_ids
+from rigs import build_model, set_option
 
 pytestmark = pytest.mark.gpu
 
@@ -32,21 +33,15 @@ def _prompts(K):
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_prefill_attention_tiles_vs_per_row(dtype):
-    from csm_mlx import _lib
     from csm_mlx.generation import FrameCache
-    from csm_mlx.models import CSM
     from csm_mlx.sampling import Sampler
-    args, w = csm_weights("tiny")
-    K = args.n_audio_codebooks
     B = len(LENS)
-    model = CSM(args, dtype=dtype, max_batch=B)
-    model.load_weights(w)
-    prompts = _prompts(K)
-    L = _lib.lib()
+    args, w, model = build_model("tiny", dtype, max_batch=B)
+    prompts = _prompts(args.n_audio_codebooks)
     D = model.backbone.args.hidden_size
 
     def run(tiles, how):
-        _lib.check(L.csm_set_option(model.engine, b"attn_prefill", 1 if tiles else 0))
+        set_option(model, "attn_prefill", 1 if tiles else 0)
         cache = FrameCache(model, B, Sampler(0.0, 0), [0] * B)
         if how == "batch":
             cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(prompts)])
@@ -66,7 +61,7 @@ def test_prefill_attention_tiles_vs_per_row(dtype):
 
     ref_h, ref_c, ref_n = run(False, "batch")
     runs = {how: run(True, how) for how in ("batch", "single", "split")}
-    _lib.check(L.csm_set_option(model.engine, b"attn_prefill", 1))
+    set_option(model, "attn_prefill", 1)
     del model
     scale = np.abs(ref_h).max(axis=1)
     for how, (h, c, n) in runs.items():
@@ -83,23 +78,17 @@ def test_prefill_attention_tiles_csm_1b_gqa4():
     busy, which the tiny backbone's G = 2 never reaches) with single-prompt prefills long enough for the tile
     path (70 and 130 rows: 2 and 3 tiles, the last partial): tiles vs the per-row attention on the same engine
     (h_last within 1e-5 of max|h|, codes identical) and codes bit-exact against the oracle."""
-    from csm_mlx import _lib
     from csm_mlx.generation import FrameCache
-    from csm_mlx.models import CSM
     from csm_mlx.sampling import Sampler
     from csm_mlx.tokenizers import tokenize_text_segment
     from helpers import prompt_ids
-    args, w = csm_weights("1b")
-    K = args.n_audio_codebooks
-    prompts = [tokenize_text_segment(prompt_ids(900 + i, n - 2), 0, K) for i, n in enumerate((70, 130))]
+    prompts = [tokenize_text_segment(prompt_ids(900 + i, n - 2), 0, 32) for i, n in enumerate((70, 130))]
     B = len(prompts)
-    model = CSM(args, dtype="bf16", max_batch=B)
-    model.load_weights(w)
-    L = _lib.lib()
+    args, w, model = build_model("1b", "bf16", max_batch=B)
     D = model.backbone.args.hidden_size
 
     def run(tiles):
-        _lib.check(L.csm_set_option(model.engine, b"attn_prefill", 1 if tiles else 0))
+        set_option(model, "attn_prefill", 1 if tiles else 0)
         cache = FrameCache(model, B, Sampler(0.0, 0), [0] * B)
         for b, (t, m) in enumerate(prompts):
             cache.prefill(b, t, m)

@@ -5,7 +5,8 @@ the same processors: greedy and sampled codes bit-exact (tiny, fp32)."""
 import numpy as np
 import pytest
 
-from helpers import csm_weights, first_divergence, oracle_for, tiny_prompt_ids
+from helpers import first_divergence, oracle_for, tiny_prompt_ids
+from rigs import build_model, codes_per_utterance
 
 pytestmark = pytest.mark.gpu
 
@@ -21,19 +22,13 @@ def penalty(hist, logits):
 
 @pytest.fixture(scope="module")
 def tiny_model():
-    from csm_mlx.models import CSM
-    args, w = csm_weights("tiny")
-    m = CSM(args, dtype="float32", max_batch=4)
-    m.load_weights(w)
+    args, w, m = build_model("tiny", "float32", max_batch=4)
     return m, oracle_for(args, w), args
 
 
 def _codes(model, prompts, frames, processors, temperature=0.0, top_k=0, seeds=None):
-    from csm_mlx.generation import generate_codes_batch
     from csm_mlx.sampling import Sampler
-    hist, n, _ = generate_codes_batch(model, prompts, frames, sampler=Sampler(temperature, top_k), seeds=seeds,
-                                      logits_processors=processors)
-    return [hist[: n[b], b] for b in range(len(prompts))]
+    return codes_per_utterance(model, prompts, frames, Sampler(temperature, top_k), seeds, processors)
 
 
 def test_identity_processor_matches_graph_path(tiny_model):

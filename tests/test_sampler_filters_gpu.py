@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from helpers import csm_weights, first_divergence, oracle_batch, oracle_for, prompt_ids, tiny_prompt_ids
+from rigs import build_model, codes_per_utterance
 
 pytestmark = pytest.mark.gpu
 
@@ -14,17 +15,11 @@ FILTERS = [dict(top_p=0.9), dict(min_p=0.05, min_tokens_to_keep=2), dict(top_k=2
            dict(top_p=0.3, min_tokens_to_keep=5)]
 
 
-def _run(model, prompts, frames, smp, seeds):
-    from csm_mlx.generation import generate_codes_batch
-    hist, n, _ = generate_codes_batch(model, prompts, frames, sampler=smp, seeds=seeds)
-    return [hist[: n[b], b].copy() for b in range(len(prompts))]
-
-
 def _check(args, w, model, prompts, frames, flt, bf16):
     from csm_mlx.sampling import make_sampler
     smp = make_sampler(0.8, **flt)
     seeds = [900 + b for b in range(len(prompts))]
-    got = _run(model, prompts, frames, smp, seeds)
+    got = codes_per_utterance(model, prompts, frames, smp, seeds)
     ref = oracle_batch(oracle_for(args, w, bf16=bf16), prompts, frames, temperature=0.8, top_k=smp.top_k,
                        seeds=seeds, top_p=smp.top_p, min_p=smp.min_p, min_keep=smp.min_tokens_to_keep)
     for b in range(len(prompts)):
@@ -34,11 +29,8 @@ def _check(args, w, model, prompts, frames, flt, bf16):
 
 @pytest.mark.parametrize("flt", FILTERS)
 def test_tiny_filters(flt):
-    from csm_mlx.models import CSM
     from csm_mlx.tokenizers import tokenize_text_segment
-    args, w = csm_weights("tiny")
-    model = CSM(args, dtype="float32", max_batch=3)
-    model.load_weights(w)
+    args, w, model = build_model("tiny", "float32", max_batch=3)
     K = args.n_audio_codebooks
     prompts = [tokenize_text_segment(tiny_prompt_ids(50 + b, 3 + b), 0, K) for b in range(3)]
     _check(args, w, model, prompts, 5, flt, bf16=False)
@@ -48,11 +40,8 @@ def test_tiny_filters(flt):
 def test_csm_1b_filters(B):
     """B = 1: the launch path (the persistent frame decoder keeps to temperature / top-k); B = 8: the
     matrix-core projections.  Every filter set, 3 frames."""
-    from csm_mlx.models import CSM
     from csm_mlx.tokenizers import tokenize_text_segment
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype="bf16", max_batch=B)
-    model.load_weights(w)
+    args, w, model = build_model("1b", "bf16", max_batch=B)
     prompts = [tokenize_text_segment(prompt_ids(60 + b, 10 + b % 3), 0, 32) for b in range(B)]
     for flt in FILTERS:
         _check(args, w, model, prompts, 3, flt, bf16=True)
@@ -86,14 +75,12 @@ def test_filter_boundaries_on_tied_rows(flt):
     each a different row and seed, so a differing kept set shows as a differing pick.  Parity is against
     the oracle's restatement; against mlx_lm it is unpinned (not importable, no sampler fixture)."""
     from csm_mlx.generation import generate_codes_batch
-    from csm_mlx.models import CSM
     from csm_mlx.sampling import make_sampler
     from csm_mlx.tokenizers import tokenize_text_segment
     from oracle.csm_oracle import sample_one
-    args, w = csm_weights("tiny")
-    B, frames, K, V = 4, 6, args.n_audio_codebooks, args.n_audio_vocab
-    model = CSM(args, dtype="float32", max_batch=B)
-    model.load_weights(w)
+    B, frames = 4, 6
+    args, w, model = build_model("tiny", "float32", max_batch=B)
+    K, V = args.n_audio_codebooks, args.n_audio_vocab
     rows = {}
 
     def proc(hist, logits):
@@ -133,13 +120,10 @@ def _check_plain_topk(args, dtype, B, frames, shapes, prompts):
     has shapes[b] = (values above the tie, width of the tie at the 5th value); every frame's c0 against the
     oracle's sample_one, no frame skipped."""
     from csm_mlx.generation import generate_codes_batch
-    from csm_mlx.models import CSM
     from csm_mlx.sampling import make_sampler
     from oracle.csm_oracle import sample_one
-    _, w = csm_weights("tiny" if dtype == "float32" else "1b")
     K, V = args.n_audio_codebooks, args.n_audio_vocab
-    model = CSM(args, dtype=dtype, max_batch=B)
-    model.load_weights(w)
+    _, _, model = build_model("tiny" if dtype == "float32" else "1b", dtype, max_batch=B)
     rows = {}
 
     def proc(hist, logits):

@@ -4,7 +4,8 @@ over (B*(S-1), K+1) rows.  fp32 weights; losses within 1e-4 relative."""
 import numpy as np
 import pytest
 
-from helpers import csm_weights, oracle_for
+from helpers import oracle_for
+from rigs import build_model
 
 pytestmark = pytest.mark.gpu
 
@@ -81,12 +82,9 @@ def test_compute_loss_multi_segment_matches_oracle(per_sample, mismatch):
     """Text rows (and masked-speaker segments) after the first scored row: utterance 0 is scored on
     its own (text rows appended to the backbone with their own masks); utterance 1 (masked speaker
     first, one scored segment last) takes the batched path -- both paths in one call."""
-    from csm_mlx.models import CSM
     from csm_mlx.scoring import _split, compute_loss
     from oracle.csm_oracle import compute_loss_ref
-    args, w = csm_weights("tiny")
-    model = CSM(args, dtype="float32", max_batch=2)
-    model.load_weights(w)
+    args, w, model = build_model("tiny", "float32", max_batch=2)
     batch = _batch_multiseg(args)
     K = args.n_audio_codebooks
     assert _split(batch["tokens"], batch["masks"], batch["loss_masks"], K)[1] == [False, True]
@@ -98,12 +96,9 @@ def test_compute_loss_multi_segment_matches_oracle(per_sample, mismatch):
 
 @pytest.mark.parametrize("per_sample,mismatch", [(False, False), (True, False), (False, True)])
 def test_compute_loss_matches_oracle(per_sample, mismatch):
-    from csm_mlx.models import CSM
     from csm_mlx.scoring import compute_loss
     from oracle.csm_oracle import compute_loss_ref
-    args, w = csm_weights("tiny")
-    model = CSM(args, dtype="float32", max_batch=2)
-    model.load_weights(w)
+    args, w, model = build_model("tiny", "float32", max_batch=2)
     batch = _batch(args)
     got = compute_loss(model, batch, per_sample=per_sample, cause_mismatch=mismatch)
     ref = compute_loss_ref(oracle_for(args, w), batch, per_sample=per_sample, cause_mismatch=mismatch)
@@ -115,12 +110,9 @@ def test_score_frames_greedy_codes_are_argmax():
     """Forcing the greedy generator's own codes reproduces its logits: arg-max of every scored
     row equals the forced code."""
     from csm_mlx.generation import generate_batch
-    from csm_mlx.models import CSM
     from csm_mlx.scoring import score_frames
     from csm_mlx.tokenizers import tokenize_text_segment
-    args, w = csm_weights("tiny")
-    model = CSM(args, dtype="float32", max_batch=2)
-    model.load_weights(w)
+    args, w, model = build_model("tiny", "float32", max_batch=2)
     p = [tokenize_text_segment([998, 21, 22, 999], 0, args.n_audio_codebooks)]
     codes = generate_batch(model, p, 8 * 80, temperature=0.0, decode=False)[0]
     logits = score_frames(model, p, [codes])
@@ -129,12 +121,9 @@ def test_score_frames_greedy_codes_are_argmax():
 
 def test_device_cross_entropy_matches_logits():
     """score_frames(logits=False) (forced_ce_kernel) equals the host cross entropy of the logits."""
-    from csm_mlx.models import CSM
     from csm_mlx.scoring import cross_entropy, score_frames
     from csm_mlx.tokenizers import tokenize_text_segment
-    args, w = csm_weights("tiny")
-    model = CSM(args, dtype="float32", max_batch=3)
-    model.load_weights(w)
+    args, w, model = build_model("tiny", "float32", max_batch=3)
     rng = np.random.default_rng(5)
     K = args.n_audio_codebooks
     p = [tokenize_text_segment([998, 30 + b, 999], 0, K) for b in range(3)]
@@ -149,13 +138,10 @@ def test_device_cross_entropy_matches_logits():
 def test_csm_1b_device_cross_entropy():
     """forced_ce_kernel at csm_1b's vocabulary (V = 2051: nine logits per thread) against the host
     cross entropy of the same logits; bf16 weights, B = 2, 4 forced rows."""
-    from csm_mlx.models import CSM
     from csm_mlx.scoring import cross_entropy, score_frames
     from csm_mlx.tokenizers import tokenize_text_segment
     from helpers import prompt_ids
-    args, w = csm_weights("1b")
-    model = CSM(args, dtype="bf16", max_batch=2)
-    model.load_weights(w)
+    args, w, model = build_model("1b", "bf16", max_batch=2)
     rng = np.random.default_rng(6)
     p = [tokenize_text_segment(prompt_ids(s), 0, 32) for s in (1, 2)]
     fr = [rng.integers(0, 2051, (4, 32)).astype(np.int32) for _ in range(2)]

@@ -10,29 +10,12 @@ import dataclasses
 import numpy as np
 import pytest
 
-from helpers import eos_weights, first_divergence, oracle_for, tiny_prompt_ids
+from helpers import eos_weights, first_divergence, oracle_for, rms
+from rigs import CAP, N_TINY, SEEDS, build_model, mimi_codec as mimi, slot_prompts
 
 pytestmark = pytest.mark.gpu
 
 PCM_RMS = 1e-4
-
-
-def rms(a, b):
-    a, b = np.asarray(a, np.float64).reshape(-1), np.asarray(b, np.float64).reshape(-1)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return float(np.sqrt(np.mean((a - b) ** 2))) if a.size else 0.0
-
-
-def mimi(name, mode, max_batch, max_frames):
-    from csm_mlx.config import MIMI_CONFIGURATION
-    from csm_mlx.mimi import MimiCodec
-    from csm_mlx.weights import synthetic_mimi_weights
-    from oracle.mimi_oracle import OracleMimi
-    m = dataclasses.replace(MIMI_CONFIGURATION[name], attn_mode=mode)
-    w = synthetic_mimi_weights(m)
-    codec = MimiCodec(m, max_batch=max_batch, max_frames=max_frames)
-    codec.load_weights(w)
-    return m, codec, OracleMimi(m, w)
 
 
 def oracle_stream(o, codes_fk, window=0):
@@ -160,28 +143,20 @@ def test_codec_slots_mimi_202407():
 
 
 # ----------------------------------------------------------------------------- 3-6. end to end, tiny CSM + tiny Mimi
-N_TINY, CAP = 14, 40
-SEEDS = [1234 + i for i in range(N_TINY)]
-
-
 @pytest.fixture(scope="module")
 def tiny():
     from csm_mlx.config import MIMI_CONFIGURATION
     from csm_mlx.mimi import MimiCodec
-    from csm_mlx.models import CSM
-    from csm_mlx.tokenizers import set_audio_tokenizer, tokenize_text_segment
+    from csm_mlx.tokenizers import set_audio_tokenizer
     from csm_mlx.weights import synthetic_mimi_weights
     from oracle.mimi_oracle import OracleMimi
-    args, w = eos_weights("tiny")
-    model = CSM(args, dtype="bf16", max_batch=8)
-    model.load_weights(w)
+    args, w, model = build_model(eos_weights("tiny"), "bf16", max_batch=8)
     mm = MIMI_CONFIGURATION["tiny"]
     mw = synthetic_mimi_weights(mm)
     codec = MimiCodec(mm, max_batch=8, max_frames=CAP)
     codec.load_weights(mw)
     set_audio_tokenizer(codec, args.n_audio_codebooks)
-    prompts = [tokenize_text_segment(tiny_prompt_ids(300 + i, 2 + i % 7), 0, args.n_audio_codebooks)
-               for i in range(N_TINY)]
+    prompts = slot_prompts(args.n_audio_codebooks)
     yield args, w, model, oracle_for(args, w, bf16=True), prompts, OracleMimi(mm, mw), codec
     del model
 

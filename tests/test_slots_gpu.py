@@ -13,26 +13,16 @@ import ctypes
 import numpy as np
 import pytest
 
-from helpers import csm_weights, eos_weights, first_divergence, oracle_for, prompt_ids, tiny_prompt_ids
+from helpers import csm_weights, eos_weights, first_divergence, oracle_for, prompt_ids
+from rigs import CAP, N_TINY, SEEDS, build_model, slot_prompts
 
 pytestmark = pytest.mark.gpu
-
-N_TINY, CAP = 14, 40
-SEEDS = [1234 + i for i in range(N_TINY)]
-
-
-def tiny_prompts(K):
-    from csm_mlx.tokenizers import tokenize_text_segment
-    return [tokenize_text_segment(tiny_prompt_ids(300 + i, 2 + i % 7), 0, K) for i in range(N_TINY)]
 
 
 @pytest.fixture(scope="module")
 def tiny():
-    from csm_mlx.models import CSM
-    args, w = eos_weights("tiny")
-    model = CSM(args, dtype="bf16", max_batch=8)
-    model.load_weights(w)
-    yield args, w, model, oracle_for(args, w, bf16=True), tiny_prompts(args.n_audio_codebooks)
+    args, w, model = build_model(eos_weights("tiny"), "bf16", max_batch=8)
+    yield args, w, model, oracle_for(args, w, bf16=True), slot_prompts(args.n_audio_codebooks)
     del model
 
 
@@ -195,12 +185,10 @@ def prompts_1b(n, K):
 def test_csm_1b_bf16_greedy(weights_1b):
     """bf16 greedy through 8 slots: 12 prompts, caps cycling 2, 3, 4, 5 (codebook steps >= 2 on dec_step_xs)."""
     from csm_mlx import generate_queue
-    from csm_mlx.models import CSM
     args, w = weights_1b
     prompts = prompts_1b(12, args.n_audio_codebooks)
     caps = [(2, 3, 4, 5)[i % 4] for i in range(12)]
-    model = CSM(args, dtype="bf16", max_batch=8)
-    model.load_weights(w)
+    model = build_model(weights_1b, "bf16", max_batch=8)[2]
     got = generate_queue(model, prompts, slots=8, max_audio_frames=caps, decode=False)
     del model
     o = oracle_for(args, w, bf16=True)
@@ -212,13 +200,11 @@ def test_csm_1b_q4_sampled(weights_1b):
     """int4 sampled (temperature 0.8, top-k 50: the sampler inside the persistent step's launch) through 8
     slots: 10 prompts, caps cycling 2, 3, 4."""
     from csm_mlx import generate_queue
-    from csm_mlx.models import CSM
     args, w = weights_1b
     prompts = prompts_1b(10, args.n_audio_codebooks)
     caps = [(2, 3, 4)[i % 3] for i in range(10)]
     seeds = [1234 + i for i in range(10)]
-    model = CSM(args, dtype="q4", max_batch=8)
-    model.load_weights(w)
+    model = build_model(weights_1b, "q4", max_batch=8)[2]
     got = generate_queue(model, prompts, slots=8, temperature=0.8, top_k=50, seeds=seeds, max_audio_frames=caps,
                          decode=False)
     del model

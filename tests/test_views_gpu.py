@@ -5,17 +5,15 @@ whose slices multiply on the GPU -- against the oracle's modules on the same wei
 import numpy as np
 import pytest
 
-from helpers import csm_weights, oracle_for
+from helpers import oracle_for
+from rigs import build_model
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bf16", "q4"])
 def test_module_views(dtype):
-    from csm_mlx.models import CSM
-    args, w = csm_weights("tiny")
-    model = CSM(args, dtype=dtype)
-    model.load_weights(w)
+    args, w, model = build_model("tiny", dtype)
     o = oracle_for(args, w, bf16=dtype == "bf16", q4=dtype == "q4")
     K, V = args.n_audio_codebooks, args.n_audio_vocab
     rng = np.random.default_rng(0)
