@@ -141,10 +141,11 @@ int csm_set_c0_processors(csm_engine* e, int n_bias, const int32_t* bias_idx, co
 int csm_prefill(csm_engine* e, int b, int T, const int32_t* tokens, const uint8_t* mask) {
   CSM_TRY {
     if (b < 0 || b >= e->B) throw CsmError(CSM_ERR_ARG, "utterance index out of range");
-    if (T <= 0 || T > e->M_cap) throw CsmError(CSM_ERR_ARG, "prompt length out of range");
+    if (T <= 0) throw CsmError(CSM_ERR_ARG, "prompt length out of range");
     const int start = e->pos_host[b] + 1;  // rows append after what the backbone already holds
-    if (start + T > e->dims.max_seq_len)
+    if (start + T > e->dims.max_seq_len)  // (before the staging cap: M_cap >= max_seq_len, so a prompt one row over is this)
       throw CsmError(CSM_ERR_TOO_LONG, "rows exceed the 2048-position window");
+    if (T > e->M_cap) throw CsmError(CSM_ERR_ARG, "prompt length out of range");
     HIPCHK(hipSetDevice(e->dev));
     const int K = e->K;
     HIPCHK(hipMemcpyAsync(e->tok, tokens, (size_t)T * (K + 1) * 4, hipMemcpyHostToDevice, e->st));
@@ -189,9 +190,10 @@ int csm_prefill_batch(csm_engine* e, int n, const int32_t* utts, const int32_t* 
       const int b = utts[i], T = Ts[i];
       if (b < 0 || b >= e->B || seen[b]) throw CsmError(CSM_ERR_ARG, "utterance index out of range or repeated");
       seen[b] = 1;
-      if (T <= 0 || T > e->M_cap) throw CsmError(CSM_ERR_ARG, "prompt length out of range");
+      if (T <= 0) throw CsmError(CSM_ERR_ARG, "prompt length out of range");
       start[i] = e->pos_host[b] + 1;
       if (start[i] + T > e->dims.max_seq_len) throw CsmError(CSM_ERR_TOO_LONG, "rows exceed the 2048-position window");
+      if (T > e->M_cap) throw CsmError(CSM_ERR_ARG, "prompt length out of range");
       row0[i + 1] = row0[i] + T;
     }
     HIPCHK(hipSetDevice(e->dev));

@@ -100,7 +100,9 @@ int csm_set_sampler_filters(csm_engine* e, double top_p, double min_p, int min_t
  * Call after csm_begin, before the first frame (csm_begin resets to off). */
 int csm_set_c0_processors(csm_engine* e, int n_bias, const int32_t* bias_idx, const float* bias_val,
                           float repetition_penalty, int repetition_context_size);
-/* Prompt rows of utterance b: tokens/mask [T][K+1] (text id in the last column). */
+/* Prompt rows of utterance b: tokens/mask [T][K+1] (text id in the last column), appended after the rows the
+ * utterance already holds.  Rows past position max_seq_len - 1: CSM_ERR_TOO_LONG, checked before anything is
+ * launched (csm_prefill_batch alike: one utterance too long refuses the whole call). */
 int csm_prefill(csm_engine* e, int b, int T, const int32_t* tokens, const uint8_t* mask);
 /* csm_prefill for several utterances at once (the rows of generate_batch's prompts): utts[i] gets
  * Ts[i] rows, rows of all of them concatenated in tokens / masks.  Up to max_seq_len rows per pass

@@ -370,6 +370,14 @@ class OracleCSM:
                                   self.ad.get("audio_embeddings"), self.dt).reshape(*tokens.shape[:2], self.K, -1)
         return np.concatenate([audio, text], axis=-2)
 
+    def embed_rows(self, tokens, mask) -> np.ndarray:
+        """generation.py:34-36: the backbone's input rows (B, T, D) of tokens / mask (B, T, K+1)."""
+        emb = self.embed_tokens(tokens) * mask[..., None].astype(self.dt)          # :34-35
+        x = np.zeros(emb.shape[:2] + emb.shape[3:], self.dt)
+        for j in range(emb.shape[2]):                                              # :36 sum over 33, in order
+            x = x + emb[:, :, j]
+        return x
+
     def frame(self, tokens, mask, cache, temperature=0.0, top_k=0, seeds=None, frame_idx=0,
               processors=None, c0_history=None, top_p=0.0, min_p=0.0, min_keep=1, sampler=None, forced=None):
         """generation.py:21-92.  tokens/mask (B,T,33).  Returns codes (B,K) int32.
@@ -383,11 +391,7 @@ class OracleCSM:
         dt = self.dt
         if forced is not None:
             forced = np.asarray(forced, np.int64).reshape(B, self.K)
-        emb = self.embed_tokens(tokens) * mask[..., None].astype(dt)               # :34-35
-        x = np.zeros(emb.shape[:2] + emb.shape[3:], dt)
-        for j in range(emb.shape[2]):                                              # :36 sum over 33, in order
-            x = x + emb[:, :, j]
-        h = self.backbone(x, cache)                                                # :39
+        h = self.backbone(self.embed_rows(tokens, mask), cache)                    # :39
         h_last = h[:, -1, :]                                                       # :40
         c0_logits = adapted_linear(h_last, self.w["codebook0_head.weight"], self.ad.get("codebook0_head"))  # :42
         for proc in processors or []:                                              # :44-49

@@ -57,10 +57,13 @@ def _oracle_for(args, weights, bf16, q4, f64=False):
     return OracleCSM(args, w, *cfg)
 
 
-def oracle_taps(o, prompts, codes):
+def oracle_taps(o, prompts, codes, block=None):
     """Teacher-forced taps of oracle ``o`` (either precision): prompts (tokens, mask) of any lengths, codes
     (F, B, K) forced per frame.  Returns h_last (F, B, D), c0_logits (F, B, V), ci_logits (F, B, K-1, V)
-    in the oracle's precision.  Utterances of equal prompt length run as one batch."""
+    in the oracle's precision.  Utterances of equal prompt length run as one batch.
+    block: a prompt of more rows reaches the backbone in pieces of ``block`` rows (the KV cache appends; the
+    last piece, of 1..block rows, is the first frame's), so the (heads, T, S) score temporaries of a long prompt
+    stay small: the same arithmetic up to the matrix products' blocking (tests/test_f64_long_cpu.py)."""
     codes = np.asarray(codes)
     F, B, K = codes.shape
     assert B == len(prompts)
@@ -72,6 +75,11 @@ def oracle_taps(o, prompts, codes):
         toks = np.stack([prompts[i][0] for i in idx]).astype(np.int64)
         msk = np.stack([prompts[i][1] for i in idx]).astype(bool)
         cache = o.new_backbone_cache()
+        if block is not None and toks.shape[1] > block:
+            ahead = (toks.shape[1] - 1) // block * block
+            for r in range(0, ahead, block):
+                o.backbone(o.embed_rows(toks[:, r:r + block], msk[:, r:r + block]), cache)
+            toks, msk = toks[:, ahead:], msk[:, ahead:]
         for f in range(F):
             s = o.frame(toks, msk, cache, forced=codes[f, idx])
             taps = [o.debug["h_last"], o.debug["c0_logits"], o.debug["ci_logits"]]
@@ -101,6 +109,24 @@ def b32_prompt_ids():
 def tiny_prompt_ids(seed: int, n_mid: int = 5):
     rng = np.random.default_rng(seed)
     return [998] + [int(x) for x in rng.integers(0, 990, n_mid)] + [999]
+
+
+def long_prompt(args, seed: int, rows: int):
+    """A seeded prompt of exactly ``rows`` rows laid out as a context segment before the text to speak: text
+    rows, then rows // 3 audio rows (codes 1 .. bins - 1 in every codebook: no row is the all-zero frame),
+    then text rows.  Returns (tokens (rows, K+1) int32, mask (rows, K+1) bool)."""
+    K, rng = args.n_audio_codebooks, np.random.default_rng(seed)
+    n_audio = rows // 3
+    a0 = (rows - n_audio) // 2
+    tokens = np.zeros((rows, K + 1), np.int32)
+    mask = np.zeros((rows, K + 1), bool)
+    audio = np.zeros(rows, bool)
+    audio[a0:a0 + n_audio] = True
+    tokens[~audio, K] = rng.integers(0, args.n_text_vocab, rows - n_audio)
+    mask[~audio, K] = True
+    tokens[audio, :K] = rng.integers(1, args.n_audio_vocab - 3, (n_audio, K))
+    mask[audio, :K] = True
+    return tokens, mask
 
 
 def rms(a, b):
@@ -266,12 +292,13 @@ def tap_errors(got, ref64):
     return out
 
 
-def f64_reference(args, weights, variant, prompts, codes):
+def f64_reference(args, weights, variant, prompts, codes, block=None):
     """(float64 taps, e32) of a case: both oracles forced on ``codes`` (F, B, K); e32[tap] = the float32
-    oracle's largest error over rows, steps and frames -- measured from the references alone."""
+    oracle's largest error over rows, steps and frames -- measured from the references alone.
+    block: ``oracle_taps``' (both oracles)."""
     kw = dict(bf16=variant == "bf16", q4=variant == "q4")
-    t64 = oracle_taps(oracle_for(args, weights, f64=True, **kw), prompts, codes)
-    t32 = oracle_taps(oracle_for(args, weights, **kw), prompts, codes)
+    t64 = oracle_taps(oracle_for(args, weights, f64=True, **kw), prompts, codes, block)
+    t32 = oracle_taps(oracle_for(args, weights, **kw), prompts, codes, block)
     return t64, {tap: float(e.max()) for tap, e in tap_errors(t32, t64).items()}
 
 

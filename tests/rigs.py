@@ -73,19 +73,38 @@ def ab(model, name, run, moved):
 TAP_NAMES = ("h_last", "c0_logits", "ci_logits")
 
 
-def frame_taps(model, prompts, frames, sampler, seeds, taps, keep=None, step=None, processors=None, prefill_batch=False):
-    """A FrameCache over ``prompts`` (tokens, mask), ``frames`` frames one at a time, the engine's ``taps`` (of
-    TAP_NAMES) read back after every frame, or only after the frames in ``keep``.  step(cache, f) runs frame f
-    in place of ``cache.run(1)``; processors: FrameCache's device pair; prefill_batch: one csm_prefill_batch
-    pass for all prompts.  Returns (hist (F, B, K), n (B,), {tap: array}) with h_last (F', B, D), c0_logits
-    (F', B, V), ci_logits (F', B, K-1, V) over the F' frames read, cut from the padded vocabulary and copied."""
-    from csm_mlx.generation import FrameCache
-    K, V, B = model.n_audio_codebooks, model.n_audio_vocab, len(prompts)
+def read_taps(model, cache, B, taps):
+    """The engine's ``taps`` (of TAP_NAMES) of ``cache``'s B utterances as they stand, in TAP_NAMES' order: h_last (B, D),
+    c0_logits (B, V), ci_logits (B, K-1, V), cut from the padded vocabulary and copied."""
+    K, V = model.n_audio_codebooks, model.n_audio_vocab
     Vp = (V + 7) // 8 * 8                                     # the engine's logits rows are padded to 8 columns
     shapes = {"h_last": (B, model.n_backbone_embedding), "c0_logits": (B, Vp), "ci_logits": (K - 1, B, Vp)}
     assert set(taps) <= set(TAP_NAMES), taps
+    out = {}
+    for t in TAP_NAMES:
+        if t in taps:
+            a = cache.debug(t, shapes[t])
+            if t != "h_last":
+                a = a[..., :V]
+            out[t] = (a.transpose(1, 0, 2) if t == "ci_logits" else a).copy()
+    return out
+
+
+def frame_taps(model, prompts, frames, sampler, seeds, taps, keep=None, step=None, processors=None, prefill_batch=False,
+               prefill=None):
+    """A FrameCache over ``prompts`` (tokens, mask), ``frames`` frames one at a time, the engine's ``taps`` (of
+    TAP_NAMES) read back after every frame, or only after the frames in ``keep``.  step(cache, f) runs frame f
+    in place of ``cache.run(1)``; processors: FrameCache's device pair; prefill_batch: one csm_prefill_batch
+    pass for all prompts; prefill(cache) feeds the prompts itself, in place of either.  Returns (hist (F, B, K),
+    n (B,), {tap: array}) with h_last (F', B, D), c0_logits (F', B, V), ci_logits (F', B, K-1, V) over the F'
+    frames read (``read_taps``)."""
+    from csm_mlx.generation import FrameCache
+    B = len(prompts)
+    assert set(taps) <= set(TAP_NAMES), taps
     cache = FrameCache(model, B, sampler, seeds, processors)
-    if prefill_batch:
+    if prefill is not None:
+        prefill(cache)
+    elif prefill_batch:
         cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(prompts)])
     else:
         for b, (t, m) in enumerate(prompts):
@@ -98,11 +117,8 @@ def frame_taps(model, prompts, frames, sampler, seeds, taps, keep=None, step=Non
             step(cache, f)
         if keep is not None and f not in keep:
             continue
-        for t in out:
-            a = cache.debug(t, shapes[t])
-            if t != "h_last":
-                a = a[..., :V]
-            out[t].append((a.transpose(1, 0, 2) if t == "ci_logits" else a).copy())
+        for t, a in read_taps(model, cache, B, taps).items():
+            out[t].append(a)
     hist, n, _ = cache.codes()
     return hist, n, {t: np.stack(v) for t, v in out.items()}
 

@@ -3,7 +3,7 @@ rig that quietly stopped checking would weaken every file that calls it.
 
 * ``ab`` runs the off leg, then the on leg, and fails unless the epoch moved by exactly the count it was given;
 * ``frame_taps`` cuts the padded vocabulary (V = 5 in rows of Vp = 8), reads only the kept frames, lets a
-  ``step`` stand in for ``cache.run(1)`` and returns copies;
+  ``step`` stand in for ``cache.run(1)`` and a ``prefill`` for the prompt feeding, and returns copies;
 * ``codes_per_utterance`` cuts every utterance at its own frame count;
 * ``handoffs`` holds the literals the test files used to carry (through test_f64_taps_gpu._expect)."""
 import ctypes
@@ -201,3 +201,11 @@ def test_handoff_table_matches_the_literals(K_, B_):
         assert _expect(K_, B_, dec_frame=df, dec_xsd=xsd, bb_step=bb) == old
     with pytest.raises(KeyError):
         handoffs("bb_xs", K_)
+
+
+def test_frame_taps_custom_prefill(cache):
+    fed = []
+    _, _, taps = frame_taps(StubModel, PROMPTS, 1, "sampler", None, ("h_last",), prefill=fed.append)
+    c = cache.made[0]
+    assert fed == [c] and not [x for x in c.log if x[0].startswith("prefill")]
+    assert np.array_equal(taps["h_last"][0], tap_value("h_last", 0))
