@@ -93,6 +93,12 @@ def lib():
             "csm_slot_restart": ([P, I, U64], I),
             "csm_slot_release": ([P, I], I),
             "csm_slot_read": ([P, I, P, I, ctypes.POINTER(I), ctypes.POINTER(ctypes.c_uint8)], I),
+            "csm_prefix_save": ([P, I, I, ctypes.POINTER(I)], I),
+            "csm_prefix_load": ([P, I, P, P], I),
+            "csm_prefix_free": ([P, I], I),
+            "csm_prefix_info": ([P, I, ctypes.POINTER(I), ctypes.POINTER(I64)], I),
+            "csm_bench_prefix_load": ([P, I, I, I, ctypes.POINTER(F), ctypes.POINTER(ctypes.c_double)], I),
+            "csm_kv_read": ([P, I, I, I, I, P, P], I),
             "csm_debug_read": ([P, ctypes.c_char_p, P, I64, ctypes.POINTER(I64)], I),
             "csm_codes_device_ptr": ([P, ctypes.POINTER(P)], I),
             "csm_read_rows": ([P, ctypes.c_char_p, I, P, P], I),

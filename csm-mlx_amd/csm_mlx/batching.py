@@ -29,6 +29,7 @@ from . import _lib
 from .generation import (FrameCache, _check_window, _decode_batch, _resolve_sampler, _seed_list,
                          device_processors)
 from .models import CSM
+from .prefix import ContextPrefix
 from .sampling import HostSampler, Sampler
 
 DEFAULT_CHUNK = 8
@@ -45,7 +46,7 @@ class StreamChunk(NamedTuple):
 
 class _EngineSlots:
     """The engine's side of a ``SlotBatch``: one ``FrameCache`` (csm_begin, the sampler filters, the c0
-    processors, the superseded check) plus the three slot calls.  ``SlotBatch`` only talks to these
+    processors, the superseded check, the prefix calls) plus the three slot calls.  ``SlotBatch`` only talks to these
     methods, so its scheduling is testable against a stub with the same ones."""
 
     def __init__(self, model: CSM, slots: int, sampler: Sampler, processors):
@@ -61,6 +62,14 @@ class _EngineSlots:
 
     def prefill(self, items: Sequence[Tuple[int, np.ndarray, np.ndarray]]):
         self.cache.prefill_batch(items)
+
+    def load_prefix(self, items: Sequence[Tuple[int, ContextPrefix]]):
+        """(slot, prefix) of every join of a boundary that has one: one csm_prefix_load, before ``prefill``."""
+        self.cache.load_prefix(items)
+
+    def save_prefix(self, b: int, rows: int, tokens, mask) -> ContextPrefix:
+        """The first ``rows`` rows slot b holds, kept as a ``ContextPrefix`` (after the boundary's ``prefill``)."""
+        return self.cache.save_prefix(b, rows, tokens, mask)
 
     def run(self, nframes: int, sync: bool = True):
         """nframes frames for every slot, waited for (the wait also checks the persistent kernels'
@@ -95,10 +104,11 @@ class _EngineSlots:
 
 
 class _Job:
-    __slots__ = ("ticket", "tokens", "mask", "cap", "seed", "ran")
+    __slots__ = ("ticket", "tokens", "mask", "cap", "seed", "ran", "prefix", "keep_rows")
 
-    def __init__(self, ticket, tokens, mask, cap, seed):
+    def __init__(self, ticket, tokens, mask, cap, seed, prefix=None, keep_rows=0):
         self.ticket, self.tokens, self.mask, self.cap, self.seed, self.ran = ticket, tokens, mask, cap, seed, 0
+        self.prefix, self.keep_rows = prefix, keep_rows
 
 
 class SlotBatch:
@@ -142,29 +152,59 @@ class SlotBatch:
         self._parked = [False] * slots
         self._joined: List[int] = []     # the slots the last ``_fill`` restarted
         self._tickets = 0
+        self._kept: dict = {}            # ticket -> ContextPrefix (None until its utterance has joined)
 
-    def submit(self, tokens, mask, max_audio_frames: int, seed: int = 0) -> int:
+    def submit(self, tokens, mask, max_audio_frames: int, seed: int = 0, *, prefix: Optional[ContextPrefix] = None,
+               keep_rows: int = 0) -> int:
         """Queue one utterance: prompt (L, K+1) tokens / mask, at most ``max_audio_frames`` frames, its
-        sampling seed.  Returns the ticket ``run`` yields its codes under."""
+        sampling seed.  Returns the ticket ``run`` yields its codes under.
+
+        ``prefix``: a ``ContextPrefix`` the prompt begins with; ``tokens`` / ``mask`` are then only the rows
+        that follow it (at least one).  Its K / V are copied into the slot when the utterance joins, and only
+        the given rows run through the backbone.  ``keep_rows`` > 0: right after the prefill of the boundary
+        at which this utterance joins, the first ``keep_rows`` rows of its whole prompt (prefix + given rows)
+        are saved as a ``ContextPrefix`` that ``kept(ticket)`` returns -- the first sentence in a new voice
+        pays for the later ones without the batch stopping.  The window guard and the frame-history check
+        count the whole prompt."""
         tokens = np.ascontiguousarray(tokens, np.int32)
         mask = np.ascontiguousarray(np.asarray(mask).astype(bool), np.uint8)
         cap = int(max_audio_frames)
         if cap < 0:
             raise ValueError("max_audio_frames must be >= 0")
-        _check_window(self.model, tokens.shape[0], cap)                          # generation.py:131-137
+        if prefix is not None:
+            prefix.require(self.model)
+            if tokens.shape[0] < 1:
+                raise ValueError("a prompt with a prefix needs at least one row after it")
+        total = tokens.shape[0] + (prefix.rows if prefix is not None else 0)
+        keep_rows = int(keep_rows)
+        if not 0 <= keep_rows <= total:
+            raise ValueError(f"keep_rows {keep_rows} outside the prompt's {total} rows")
+        _check_window(self.model, total, cap)                                    # generation.py:131-137
         if cap > self.max_frames:     # the engine would refuse the frames that take it there (CSM_ERR_STATE)
             raise _lib.CsmHipError(_lib.CSM_ERR_STATE, f"an utterance of up to {cap} frames does not fit the engine's "
                                    f"{self.max_frames}-frame code history (CSM(..., max_frames=))")
         ticket = self._tickets
         self._tickets += 1
-        self._queue.append(_Job(ticket, tokens, mask, cap, seed))
+        self._queue.append(_Job(ticket, tokens, mask, cap, seed, prefix, keep_rows if cap > 0 else 0))
+        if keep_rows and cap > 0:
+            self._kept[ticket] = None
         return ticket
+
+    def kept(self, ticket: int) -> ContextPrefix:
+        """The ``ContextPrefix`` saved for a ticket submitted with ``keep_rows`` (available once its utterance
+        has joined the batch: from the first event ``run`` / ``stream`` yields after that boundary on)."""
+        if ticket not in self._kept:
+            raise ValueError(f"ticket {ticket} was not submitted with keep_rows (or generates no frames)")
+        if self._kept[ticket] is None:
+            raise RuntimeError(f"ticket {ticket} has not joined the batch yet: its rows are not prefilled")
+        return self._kept[ticket]
 
     def _fill(self) -> Generator[Tuple[int, np.ndarray], None, None]:
         """A frame boundary: free slots take the next queued prompts (all of the boundary's joins in one
-        batched prefill); slots left without work are parked."""
+        batched prefill, after one load of all their prefixes; then the ``keep_rows`` saves); slots left
+        without work are parked."""
         K = self.model.n_audio_codebooks
-        joins = []
+        joins, loads, saves = [], [], []
         self._joined = []
         for b in range(self.slots):
             if self._active[b] is not None:
@@ -177,12 +217,23 @@ class SlotBatch:
                 self._active[b] = job
                 self._parked[b] = False
                 joins.append((b, job.tokens, job.mask))
+                if job.prefix is not None:
+                    loads.append((b, job.prefix))
+                if job.keep_rows:
+                    saves.append((b, job))
                 self._joined.append(b)
             elif not self._parked[b]:
                 self._eng.release(b)
                 self._parked[b] = True
+        if loads:
+            self._eng.load_prefix(loads)
         if joins:
             self._eng.prefill(joins)
+        for b, job in saves:
+            t, m = job.tokens, job.mask.astype(bool)
+            if job.prefix is not None:
+                t, m = np.concatenate([job.prefix.tokens, t], 0), np.concatenate([job.prefix.mask, m], 0)
+            self._kept[job.ticket] = self._eng.save_prefix(b, job.keep_rows, t[: job.keep_rows], m[: job.keep_rows])
 
     def _chunk_frames(self) -> int:
         """The frames of the next chunk: ``chunk``, shortened to the smallest remaining budget among the
@@ -289,29 +340,35 @@ class SlotBatch:
 
 
 def _queued(model, prompts, max_audio_length_ms, slots, temperature, top_k, sampler, seeds, max_audio_frames,
-            logits_processors, chunk) -> Tuple[SlotBatch, List[int]]:
+            logits_processors, chunk, prefixes=None) -> Tuple[SlotBatch, List[int]]:
     """What both queue entry points begin with: a ``SlotBatch`` with every prompt submitted under its frame
-    cap and seed.  Returns (batch, the tickets in prompt order)."""
+    cap, seed and prefix.  Returns (batch, the tickets in prompt order)."""
     smp = _resolve_sampler(temperature, sampler, top_k)
     n = len(prompts)
     caps = [int(max_audio_length_ms / 80)] * n if max_audio_frames is None else [int(c) for c in max_audio_frames]
     if len(caps) != n:
         raise ValueError("need one frame cap per prompt")
+    if prefixes is None:
+        prefixes = [None] * n
+    if len(prefixes) != n:
+        raise ValueError("need one prefix (or None) per prompt")
     seed_list = _seed_list(seeds, n)
     batch = SlotBatch(model, slots, sampler=smp, logits_processors=logits_processors, chunk=chunk)
-    return batch, [batch.submit(t, m, caps[i], int(seed_list[i])) for i, (t, m) in enumerate(prompts)]
+    return batch, [batch.submit(t, m, caps[i], int(seed_list[i]), prefix=prefixes[i]) for i, (t, m) in enumerate(prompts)]
 
 
 def generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], max_audio_length_ms: float = 10_000,
                    *, slots: int, temperature: float = 0.0, top_k: int = 0, sampler=None, seeds=None,
                    max_audio_frames: Optional[Sequence[int]] = None, decode: bool = True, with_codes: bool = False,
-                   logits_processors: Optional[List[Callable]] = None, chunk: int = DEFAULT_CHUNK):
+                   logits_processors: Optional[List[Callable]] = None, chunk: int = DEFAULT_CHUNK,
+                   prefixes: Optional[Sequence[Optional[ContextPrefix]]] = None):
     """``generate_batch`` for any number of prompts through ``slots`` slots: list of waveforms in prompt
     order (or codes if decode=False; (codes, waveforms) with ``with_codes``).  ``max_audio_frames``: one
     frame cap per prompt (default: ``max_audio_length_ms`` for all).  Seeds follow ``generate_batch``: a
-    scalar s gives s + i for prompt i."""
+    scalar s gives s + i for prompt i.  ``prefixes``: one ``ContextPrefix`` (or None) per prompt, which then
+    holds only the rows after it (``SlotBatch.submit``)."""
     batch, tickets = _queued(model, prompts, max_audio_length_ms, slots, temperature, top_k, sampler, seeds,
-                             max_audio_frames, logits_processors, chunk)
+                             max_audio_frames, logits_processors, chunk, prefixes)
     got = dict(batch.run())
     codes = [got[t] for t in tickets]
     if not decode:
@@ -328,14 +385,15 @@ def generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]],
 def stream_generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]],
                           max_audio_length_ms: float = 10_000, *, slots: int, temperature: float = 0.0,
                           top_k: int = 0, sampler=None, seeds=None, max_audio_frames: Optional[Sequence[int]] = None,
-                          logits_processors: Optional[List[Callable]] = None, chunk: int = DEFAULT_CHUNK
+                          logits_processors: Optional[List[Callable]] = None, chunk: int = DEFAULT_CHUNK,
+                          prefixes: Optional[Sequence[Optional[ContextPrefix]]] = None
                           ) -> Generator[Tuple[int, np.ndarray, bool], None, None]:
     """``generate_queue`` as a stream: yields ``(prompt index, pcm, final)`` while the queue runs -- ``pcm``
     the new (v * 1920,) float32 samples of that prompt's utterance (v >= 0), ``final`` on its last event.  The
     concatenation per prompt is what ``stream_generate`` yields for it alone.  The registered audio tokenizer
     needs ``max_batch >= slots`` and ``max_frames >=`` the largest frame cap."""
     batch, tickets = _queued(model, prompts, max_audio_length_ms, slots, temperature, top_k, sampler, seeds,
-                             max_audio_frames, logits_processors, chunk)
+                             max_audio_frames, logits_processors, chunk, prefixes)
     index = {t: i for i, t in enumerate(tickets)}
     for ev in batch.stream():
         yield index[ev.ticket], ev.pcm, ev.final

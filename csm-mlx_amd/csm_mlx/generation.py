@@ -18,12 +18,13 @@ import contextlib
 import ctypes
 import os
 import time
-from typing import Any, Callable, Generator, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Generator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
 from . import _lib
 from .models import CSM
+from .prefix import ContextPrefix
 from .sampling import C0_WINDOW_MAX, HostSampler, LogitBias, RepetitionPenalty, Sampler
 from .segment import Segment
 from .tokenizers import decode_audio, get_audio_tokenizer, tokenize_segment, tokenize_text_segment
@@ -130,6 +131,32 @@ class FrameCache:
         toks = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int32) for _, t, _ in items]), np.int32)
         msks = np.ascontiguousarray(np.concatenate([np.asarray(m, np.uint8) for _, _, m in items]), np.uint8)
         self._call("csm_prefill_batch", len(items), _lib.ptr(utts), _lib.ptr(Ts), _lib.ptr(toks), _lib.ptr(msks))
+
+    def save_prefix(self, b: int, rows: int, tokens, mask) -> ContextPrefix:
+        """The backbone K / V of the first ``rows`` rows utterance b holds, kept on the GPU
+        (csm_prefix_save); ``tokens`` / ``mask`` (rows, K+1) are the rows they stand for.  The batch goes on
+        as if this had not been called."""
+        h = ctypes.c_int(0)
+        self._call("csm_prefix_save", b, int(rows), ctypes.byref(h))
+        nbytes = ctypes.c_int64(0)
+        self._call("csm_prefix_info", h.value, None, ctypes.byref(nbytes))
+        model, L = self.model, self.L
+
+        def release(handle):       # (a model whose engine is gone has freed its prefixes with it)
+            if getattr(model, "_engine", None) is not None:
+                L.csm_prefix_free(model.engine, handle)
+        return ContextPrefix(model, h.value, rows, nbytes.value, tokens, mask, release)
+
+    def load_prefix(self, items: Sequence[Tuple[int, ContextPrefix]]):
+        """Copy each prefix into its (empty) utterance's cache, all in one launch (csm_prefix_load): items =
+        (b, prefix) with distinct b; follow with the prefill of each utterance's remaining rows."""
+        if not items:
+            return self._check()
+        for _, p in items:
+            p.require(self.model)
+        utts = np.array([b for b, _ in items], np.int32)
+        ids = np.array([p.handle for _, p in items], np.int32)
+        self._call("csm_prefix_load", len(items), _lib.ptr(utts), _lib.ptr(ids))
 
     def run(self, nframes: int, sync: bool = True) -> bool:
         """Enqueue nframes frame graphs; with sync, wait and return whether every utterance is done
@@ -271,10 +298,14 @@ def generate_frame(model: CSM, tokens, *, temperature: float = 0.8, token_mask=N
     return cache.last_codes()
 
 
-def build_prompt(model: CSM, text, speaker: int, context: Sequence[Segment]):
-    """generation.py:108-125 -> (L, K+1) tokens, mask."""
+def build_prompt(model: CSM, text, speaker: int, context: Union[Sequence[Segment], ContextPrefix]):
+    """generation.py:108-125 -> (L, K+1) tokens, mask.  With a ``ContextPrefix`` as context: the text
+    segment's rows alone (the prefix stands for the rest)."""
     K = model.n_audio_codebooks
     toks, masks = [], []
+    if isinstance(context, ContextPrefix):
+        context.require(model)
+        context = ()
     for seg in context:
         t, m = tokenize_segment(seg, n_audio_codebooks=K)
         toks.append(t)
@@ -292,15 +323,27 @@ def _check_window(model: CSM, L: int, max_audio_frames: int):
 
 
 def _start(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], max_audio_frames: int, sampler, seeds,
-           logits_processors, batched_prefill: bool):
+           logits_processors, batched_prefill: bool, prefixes: Optional[Sequence[Optional[ContextPrefix]]] = None):
     """What every frame loop begins with: the window guard on every prompt (before any engine call), a
     ``FrameCache`` of one utterance per prompt with the processors the GPU takes (``device_processors``),
     and the prompts' prefill -- one csm_prefill_batch pass, or csm_prefill of the only prompt.  Returns
-    (cache, the processors left for the host: None when the GPU took them)."""
-    for t, _ in prompts:
-        _check_window(model, t.shape[0], max_audio_frames)
+    (cache, the processors left for the host: None when the GPU took them).
+    ``prefixes``: one ``ContextPrefix`` or None per prompt; a prompt with one holds only the rows that follow
+    it.  All of them are loaded in one csm_prefix_load before the one prefill, and the window guard counts
+    prefix + prompt rows."""
+    if prefixes is None:
+        prefixes = [None] * len(prompts)
+    if len(prefixes) != len(prompts):
+        raise ValueError("need one prefix (or None) per prompt")
+    for (t, _), p in zip(prompts, prefixes):
+        if p is not None:
+            p.require(model)
+        _check_window(model, t.shape[0] + (p.rows if p is not None else 0), max_audio_frames)
     on_device = device_processors(logits_processors, sampler)
     cache = FrameCache(model, len(prompts), sampler, seeds, on_device)
+    loads = [(b, p) for b, p in enumerate(prefixes) if p is not None]
+    if loads:       # (a call without a prefix makes the engine calls it always made)
+        cache.load_prefix(loads)
     if batched_prefill:
         cache.prefill_batch([(b, t, m) for b, (t, m) in enumerate(prompts)])
     else:
@@ -321,8 +364,11 @@ def _mark(timings: Optional[dict], key: str, t0: float, model: Optional[CSM] = N
 
 def generate_codes_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], max_audio_frames: int, *,
                          sampler: Sampler, seeds=None, chunk: int = 8,
-                         logits_processors: Optional[List[Callable]] = None, timings: Optional[dict] = None):
+                         logits_processors: Optional[List[Callable]] = None, timings: Optional[dict] = None,
+                         prefixes: Optional[Sequence[Optional[ContextPrefix]]] = None):
     """Run the frame loop for B prompts.  Returns (hist [F,B,K], n_frames [B], cache).
+    ``prefixes``: one ``ContextPrefix`` (or None) per prompt, loaded in front of it: the prompt is then only
+    the rows that follow the prefix (``_start``).
     ``logits_processors`` from ``make_logits_processors`` run on the GPU inside the frame
     (``device_processors``); with any other list every frame pauses after codebook0_head for the host
     (generation.py:44-49).
@@ -330,7 +376,8 @@ def generate_codes_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndar
     its "prefill" / "frames" entries (the engine is synchronized at each boundary)."""
     t0 = time.perf_counter()
     # B > 1: every prompt's rows through one pass of each projection (weights streamed once)
-    cache, processors = _start(model, prompts, max_audio_frames, sampler, seeds, logits_processors, len(prompts) > 1)
+    cache, processors = _start(model, prompts, max_audio_frames, sampler, seeds, logits_processors, len(prompts) > 1,
+                               prefixes)
     t0 = _mark(timings, "prefill", t0, model)
     left = max_audio_frames
     if isinstance(sampler, HostSampler) or processors:   # the host in every frame: frame by frame
@@ -369,15 +416,22 @@ def _decode_batch(model: CSM, hist: np.ndarray, n_frames: np.ndarray) -> List[np
     return out
 
 
-def generate(model: CSM, text, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000, *,
+def _prefixes_of(context):
+    """``prefixes=`` of a one-prompt call whose ``context`` may be a ``ContextPrefix``."""
+    return [context] if isinstance(context, ContextPrefix) else None
+
+
+def generate(model: CSM, text, speaker: int, context: Union[List[Segment], ContextPrefix],
+             max_audio_length_ms: float = 90_000, *,
              temperature: float = 0.8, logits_processors: Optional[List[Callable]] = None,
              stream: Any = default_stream, sampler=None, seed=None) -> np.ndarray:
-    """generation.py:95-178: returns the (F*1920,) float32 waveform (or zeros((0,)) + warning)."""
+    """generation.py:95-178: returns the (F*1920,) float32 waveform (or zeros((0,)) + warning).
+    ``context`` may be a ``ContextPrefix`` (``cache_context``) in place of the segment list it was made of."""
     max_audio_frames = int(max_audio_length_ms / 80)
     prompt = build_prompt(model, text, speaker, context)
     smp = _resolve_sampler(temperature, sampler)
     hist, n_frames, _ = generate_codes_batch(model, [prompt], max_audio_frames, sampler=smp, seeds=seed,
-                                             logits_processors=logits_processors)
+                                             logits_processors=logits_processors, prefixes=_prefixes_of(context))
     if n_frames[0] == 0:
         print("[WARN] No samples generated.")
         return np.zeros((0,), dtype=np.float32)
@@ -387,13 +441,14 @@ def generate(model: CSM, text, speaker: int, context: List[Segment], max_audio_l
 def generate_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], max_audio_length_ms: float = 10_000,
                    *, temperature: float = 0.0, top_k: int = 0, sampler=None, seeds=None, decode: bool = True,
                    with_codes: bool = False, timings: Optional[dict] = None,
-                   logits_processors: Optional[List[Callable]] = None):
+                   logits_processors: Optional[List[Callable]] = None,
+                   prefixes: Optional[Sequence[Optional[ContextPrefix]]] = None):
     """Batched extension: B prompts (tokens, mask) -> list of waveforms (or codes if decode=False;
     (codes, waveforms) with ``with_codes``).  ``timings``: per-phase wall seconds (prefill, frames,
-    decode) added to the dict."""
+    decode) added to the dict.  ``prefixes``: as in ``generate_codes_batch``."""
     smp = _resolve_sampler(temperature, sampler, top_k)
     hist, n_frames, _ = generate_codes_batch(model, prompts, int(max_audio_length_ms / 80), sampler=smp, seeds=seeds,
-                                             timings=timings, logits_processors=logits_processors)
+                                             timings=timings, logits_processors=logits_processors, prefixes=prefixes)
     codes = [hist[: n_frames[b], b] for b in range(len(prompts))]
     if not decode:
         return codes
@@ -434,11 +489,12 @@ def _host_paced_frames(cache: "FrameCache", codec, max_audio_frames: int, proces
 
 
 def _stream_frames(model: CSM, prompts, max_audio_frames: int, sampler, seeds, logits_processors,
-                   batched_prefill: bool):
+                   batched_prefill: bool, prefixes=None):
     """The body of both streaming entry points: ``_start``, then the mode's frame generator between two
     resets of the codec's streaming state (the second also when the consumer closes the stream early)."""
     codec = get_audio_tokenizer(model.n_audio_codebooks)
-    cache, processors = _start(model, prompts, max_audio_frames, sampler, seeds, logits_processors, batched_prefill)
+    cache, processors = _start(model, prompts, max_audio_frames, sampler, seeds, logits_processors, batched_prefill,
+                               prefixes)
     B = len(prompts)
     codec.reset_state(B)
     try:
@@ -452,16 +508,18 @@ def _stream_frames(model: CSM, prompts, max_audio_frames: int, sampler, seeds, l
 
 def stream_generate_batch(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]],
                           max_audio_length_ms: float = 10_000, *, temperature: float = 0.8, top_k: int = 0,
-                          sampler=None, seeds=None, logits_processors: Optional[List[Callable]] = None
+                          sampler=None, seeds=None, logits_processors: Optional[List[Callable]] = None,
+                          prefixes: Optional[Sequence[Optional[ContextPrefix]]] = None
                           ) -> Generator[Tuple[np.ndarray, np.ndarray], None, None]:
     """Batched extension of ``stream_generate`` (generation.py:181-258): per frame yields
     (pcm (B, 1920) float32 from the codec's streaming ``decode_step``, done (B,) bool).  An
     utterance's rows after its EOS frame are not audio (its ``done`` flag is set)."""
     yield from _stream_frames(model, prompts, int(max_audio_length_ms / 80),
-                              _resolve_sampler(temperature, sampler, top_k), seeds, logits_processors, True)
+                              _resolve_sampler(temperature, sampler, top_k), seeds, logits_processors, True, prefixes)
 
 
-def stream_generate(model: CSM, text, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
+def stream_generate(model: CSM, text, speaker: int, context: Union[List[Segment], ContextPrefix],
+                    max_audio_length_ms: float = 90_000,
                     *, temperature: float = 0.8, logits_processors: Optional[List[Callable]] = None,
                     stream: Any = default_stream, sampler=None, seed=None) -> Generator[np.ndarray, None, None]:
     """generation.py:181-258: yields (1920,) float32 PCM per generated frame.
@@ -471,6 +529,6 @@ def stream_generate(model: CSM, text, speaker: int, context: List[Segment], max_
     prompt = build_prompt(model, text, speaker, context)
     with contextlib.closing(_stream_frames(model, [prompt], int(max_audio_length_ms / 80),
                                            _resolve_sampler(temperature, sampler), seed, logits_processors,
-                                           False)) as frames:     # (closed with this generator: the codec reset)
+                                           False, _prefixes_of(context))) as frames:     # (closed with this generator: the codec reset)
         for pcm, _ in frames:
             yield pcm[0]

@@ -3,7 +3,8 @@
 //   csm_engine_weights.hip  lifecycle and weights: create / destroy, loader, quantizer, derived tables
 //   csm_engine_abi.hip      frame ABI: csm_begin, prefill, csm_run_frames*, csm_frame_*, csm_read_codes
 //   csm_engine_slots.hip    continuous batching: csm_slot_restart / csm_slot_release / csm_slot_read
-//   csm_engine_lab.hip      lab and inspection: csm_bench_*, debug taps, csm_linear, csm_set_option
+//   csm_engine_prefix.hip   shared context prefixes: csm_prefix_save / csm_prefix_load / csm_prefix_free / csm_prefix_info
+//   csm_engine_lab.hip      lab and inspection: csm_bench_*, debug taps, csm_linear, csm_kv_read, csm_set_option
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -86,6 +87,13 @@ struct Handoff {
 };
 // csm_set_option / csm_debug_read keys of csm_engine::handoffs(), in its order
 constexpr const char* HANDOFF_KEYS[3] = {"dec_frame", "bb_step", "dec_xsd"};
+
+// One join of the prefix copy kernel (csm_engine_prefix.hip): `rows` positions of slot b's backbone caches
+// against the compact store [layer][k|v][Hkv][rows][hd] at `store`
+struct PrefixJoin {
+  float* store;
+  int b, rows;
+};
 
 #pragma GCC visibility pop
 
@@ -185,6 +193,24 @@ struct csm_engine {
   bool slot_mode = false;     // from the first slot call after csm_begin until the next csm_begin
   std::vector<char> parked_host;
   std::vector<int> slot_first;
+  // Shared context prefixes (csm_engine_prefix.hip): saved backbone K / V rows of a prompt's first positions,
+  // each in a hipMalloc of its own (not in batch_allocs: a growing batch keeps them), by handle.  A prefix is
+  // valid for the weights and RoPE table it was computed with: weights_epoch counts every change of either
+  // (csm_load_tensor, csm_quantize, csm_set_rope_table, csm_weights_received), batch_epoch is its value at the
+  // last csm_begin -- what the rows in the caches were computed with -- and a prefix records the latter.
+  struct Prefix {
+    float* buf = nullptr;
+    int rows = 0;
+    unsigned long long epoch = 0;
+  };
+  std::map<int, Prefix> prefixes;
+  int prefix_next = 1;
+  unsigned long long weights_epoch = 0, batch_epoch = 0;
+  float** kv_tab = nullptr;  // device [2 * backbone layers]: layer l's kc at 2 l, vc at 2 l + 1 (ensure_batch)
+  PrefixJoin* prefix_desc = nullptr;  // device [prefix_cap] joins of one copy launch
+  PrefixJoin* prefix_pin = nullptr;   // their pinned staging; prefix_ev: its last upload has been read
+  int prefix_cap = 0;
+  hipEvent_t prefix_ev = nullptr;
   // graphs
   hipGraphExec_t g_body = nullptr, g_head = nullptr;
   int g_B = -1;
@@ -255,6 +281,9 @@ struct csm_engine {
       if (ev) (void)hipEventDestroy(ev);
     if (ahead_pin) (void)hipHostFree(ahead_pin);
     if (ptiles_pin) (void)hipHostFree(ptiles_pin);
+    if (prefix_pin) (void)hipHostFree(prefix_pin);
+    if (prefix_ev) (void)hipEventDestroy(prefix_ev);
+    for (auto& kv : prefixes) (void)hipFree(kv.second.buf);
     if (g_body) (void)hipGraphExecDestroy(g_body);
     if (g_head) (void)hipGraphExecDestroy(g_head);
     for (void* p : allocs) (void)hipFree(p);

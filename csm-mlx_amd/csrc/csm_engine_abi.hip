@@ -61,6 +61,7 @@ int csm_begin(csm_engine* e, int B, const uint64_t* seeds, float temperature, in
     ensure_batch(e, B);
     if (e->tiled_dirty) build_tiled(e);
     if (e->proj_tab_dirty) build_proj_table(e);
+    e->batch_epoch = e->weights_epoch;
     e->pos_host.assign(B, -1);
     e->B = B;
     e->temperature = temperature;

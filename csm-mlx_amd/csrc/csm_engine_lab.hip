@@ -70,6 +70,22 @@ int csm_debug_read(csm_engine* e, const char* what, void* host, int64_t nbytes, 
   CSM_CATCH
 }
 
+int csm_kv_read(csm_engine* e, int b, int layer, int first, int rows, float* k, float* v) {
+  CSM_TRY {
+    if (!e) throw CsmError(CSM_ERR_ARG, "null engine");
+    const Stack& s = e->bb;
+    if (b < 0 || b >= e->B || layer < 0 || layer >= s.d.n_layers || first < 0 || rows < 1 || first + rows > s.S_cap)
+      throw CsmError(CSM_ERR_ARG, "csm_kv_read: utterance, layer or positions out of range");
+    HIPCHK(hipSetDevice(e->dev));
+    HIPCHK(hipStreamSynchronize(e->st));
+    const size_t hd = s.d.head_dim, Hkv = s.d.n_kv_heads, run = (size_t)rows * hd * 4, pitch = (size_t)s.S_cap * hd * 4;
+    const size_t off = ((size_t)b * Hkv * s.S_cap + first) * hd;
+    if (k) HIPCHK(hipMemcpy2D(k, run, s.L[layer].kc + off, pitch, run, Hkv, hipMemcpyDeviceToHost));
+    if (v) HIPCHK(hipMemcpy2D(v, run, s.L[layer].vc + off, pitch, run, Hkv, hipMemcpyDeviceToHost));
+  }
+  CSM_CATCH
+}
+
 int csm_read_rows(csm_engine* e, const char* name, int n, const int32_t* rows, float* out) {
   CSM_TRY {
     if (!name || n < 0 || (n > 0 && (!rows || !out))) throw CsmError(CSM_ERR_ARG, "bad csm_read_rows arguments");

@@ -49,6 +49,12 @@ void ensure_batch(csm_engine* e, int B) {
       l.vc = (float*)e->balloc(kv);
     }
   }
+  {  // the prefix copy kernel's table of the backbone caches (csm_engine_prefix.hip)
+    std::vector<float*> tab;
+    for (LayerW& l : e->bb.L) { tab.push_back(l.kc); tab.push_back(l.vc); }
+    if (!e->kv_tab) e->kv_tab = (float**)e->alloc(tab.size() * sizeof(float*));
+    HIPCHK(hipMemcpy(e->kv_tab, tab.data(), tab.size() * sizeof(float*), hipMemcpyHostToDevice));
+  }
   e->h_last = (float*)e->balloc(Bm * D * 4);
   e->c0_logits = (float*)e->balloc(Bm * Vp * 4);
   e->force = (int*)e->balloc(Bm * K * 4);
@@ -418,6 +424,7 @@ int csm_set_rope_table(csm_engine* e, int which, const float* table, int n_pos, 
     if (head_dim != s.d.head_dim || n_pos < s.S_cap) throw CsmError(CSM_ERR_ARG, "rope table shape mismatch");
     HIPCHK(hipSetDevice(e->dev));
     HIPCHK(hipMemcpy(s.rope, table, (size_t)s.S_cap * head_dim * 4, hipMemcpyHostToDevice));
+    ++e->weights_epoch;  // saved prefixes hold keys rotated by the old table
   }
   CSM_CATCH
 }
@@ -434,6 +441,7 @@ int csm_load_tensor(csm_engine* e, const char* cname, const void* host, int src_
     };
     if (name.rfind("decoder.layers.0.", 0) == 0) e->proj_tab_dirty = true;  // feeds the folded layer-0 QKV table
     e->tiled_dirty = true;
+    ++e->weights_epoch;  // saved prefixes are stale from here on
     if (e->wdt == WDT_Q4 && load_q4(e, name, host, src_dtype, shp)) return CSM_OK;
     if (src_dtype == CSM_U32) throw CsmError(CSM_ERR_ARG, "packed int4 tensor " + name + " needs a CSM_Q4 engine");
     const size_t es = e->wsz;
@@ -593,6 +601,7 @@ int csm_weights_received(csm_engine* e) {
     for (const auto& nm : e->required) e->loaded.insert(nm);
     e->tiled_dirty = true;
     e->proj_tab_dirty = true;
+    ++e->weights_epoch;
     e->g_B = -1;
   }
   CSM_CATCH
@@ -641,6 +650,7 @@ int csm_quantize(csm_engine* e, int group_size, int bits) {
     e->tiled_bufs.clear();
     e->ws.tiled.clear();
     e->tiled_dirty = true;
+    ++e->weights_epoch;
     e->g_B = -1;
   }
   CSM_CATCH

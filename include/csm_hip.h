@@ -173,6 +173,35 @@ int csm_read_codes(csm_engine* e, int32_t* hist, int32_t* n_frames, uint8_t* don
 int csm_slot_restart(csm_engine* e, int b, uint64_t seed);
 int csm_slot_release(csm_engine* e, int b);
 int csm_slot_read(csm_engine* e, int b, int32_t* codes, int cap_frames, int* n_frames, uint8_t* done);
+/* Shared context prefixes (no reference counterpart: the reference's generate() pushes every context segment
+ * through the backbone again for each sentence, generation.py:108-125).  Attention is causal, so the backbone
+ * K / V of a prompt's first P rows depend on those rows alone: they are saved once and loaded into any
+ * utterance or slot that begins with the same rows, which then prefills only what follows (csm_prefill* append
+ * after the rows an utterance holds).  A prefix is a compact device buffer [layer][k|v][Hkv][rows][hd] fp32
+ * owned by the engine until csm_prefix_free or csm_engine_destroy; a growing batch does not lose it.
+ *   csm_prefix_save  positions 0 .. rows-1 of utterance b's backbone caches, every layer -> *id (a small
+ *                    handle).  Right after a prefill or in the middle of an utterance; the batch goes on as
+ *                    if it had not been called.  Only rows that have reached the cache count (the row of the
+ *                    last frame's codes has not until the next frame runs): CSM_ERR_ARG unless
+ *                    1 <= rows <= rows held; CSM_ERR_STATE when b holds none (fresh, restarted or parked).
+ *   csm_prefix_load  for n distinct utterances at once: prefix ids[i] -> utterance utts[i], positions
+ *                    0 .. rows-1, and its position becomes rows - 1; one launch on the engine stream for all n,
+ *                    not waited for.  The utterance still has no prompt: frames stay CSM_ERR_STATE
+ *                    ("csm_prefill not called") until at least one more row is prefilled.  Several utterances
+ *                    may load the same prefix.  Works after csm_begin and after csm_slot_restart.  Refused
+ *                    before anything is launched, every utterance left as it was: CSM_ERR_STATE when an
+ *                    utterance already holds rows, between csm_frame_c0_logits and csm_frame_finish, or for
+ *                    a stale prefix; CSM_ERR_ARG for an unknown handle or an utterance out of range or
+ *                    repeated; CSM_ERR_TOO_LONG when rows >= max_seq_len.
+ *   csm_prefix_free  waits for the engine stream (a load in flight still reads the buffer), then releases it.
+ *   csm_prefix_info  *rows and *bytes of a prefix (either may be NULL).
+ * A prefix is valid for the weights and the RoPE table it was computed with: after csm_load_tensor (adapters
+ * included), csm_quantize, csm_set_rope_table or csm_weights_received every older prefix is stale -- it cannot
+ * be loaded, csm_prefix_info still answers for it and csm_prefix_free still frees it. */
+int csm_prefix_save(csm_engine* e, int b, int rows, int* id);
+int csm_prefix_load(csm_engine* e, int n, const int32_t* utts, const int32_t* ids);
+int csm_prefix_free(csm_engine* e, int id);
+int csm_prefix_info(csm_engine* e, int id, int* rows, int64_t* bytes);
 /* Debug / parity taps: "h_last" [B][D], "c0_logits" [B][Vpad], "ci_logits" [K-1][B][Vpad], "codes" [B][K],
  * "audio_head" [K-1][Vpad][Dd] (f32 or bf16 bits),
  * "weight:<MLX name>" a whole (unfused) Linear / Embedding matrix in its device layout (int4: nibbles

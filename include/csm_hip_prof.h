@@ -40,6 +40,17 @@ int csm_bench_bb_step(csm_engine* e, int iters, float* avg_us, double* bytes);
  * when the step kernel is not active on this engine. */
 int csm_bench_dec_xsd(csm_engine* e, int iters, float* avg_us, double* bytes);
 
+/* csm_prefix_load of prefix `id` into the empty utterance b (its checks and its effect), then the same copy
+ * launch replayed `iters` times (same bytes to the same place), timed with HIP events on the engine stream.
+ * *bytes = the prefix's bytes read once + written once. */
+int csm_bench_prefix_load(csm_engine* e, int b, int id, int iters, float* avg_us, double* bytes);
+
+/* Inspection door of the backbone KV caches: positions first .. first+rows-1 of utterance b in layer `layer`,
+ * as k / v [Hkv][rows][hd] float32 (either may be NULL).  Waits for the engine stream.  CSM_ERR_ARG for an
+ * utterance, layer or position range outside the engine's.  The tests of the prefix calls read the caches
+ * through it; the product does not call it. */
+int csm_kv_read(csm_engine* e, int b, int layer, int first, int rows, float* k, float* v);
+
 /* Tuning / debug switches (re-capture the frame graphs), per engine: "fold_proj" (decoder steps >= 2
  * gather projection(E_a[c]) from a table built at csm_begin, default 1), "qkv0_tab" (decoder layer 0's
  * q, k, v gathered from a table at steps >= 2, default 1), "qkv0_tab_batched" (0: batched frames run
