@@ -43,6 +43,14 @@ class MimiDims(ctypes.Structure):
                 ("norm_eps", ctypes.c_float), ("gelu_erf", ctypes.c_int), ("attn_mode", ctypes.c_int)]
 
 
+class CsmSampling(ctypes.Structure):
+    """csm_sampling (csm_slot_set_sampling): one utterance's sampler and c0 processors."""
+    _fields_ = [("temperature", ctypes.c_float), ("top_k", ctypes.c_int), ("top_p", ctypes.c_double),
+                ("min_p", ctypes.c_double), ("min_tokens_to_keep", ctypes.c_int), ("n_bias", ctypes.c_int),
+                ("bias_idx", ctypes.POINTER(ctypes.c_int32)), ("bias_val", ctypes.POINTER(ctypes.c_float)),
+                ("repetition_penalty", ctypes.c_float), ("repetition_context_size", ctypes.c_int)]
+
+
 class CsmHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(msg)
@@ -93,7 +101,8 @@ def lib():
             "csm_slot_restart": ([P, I, U64], I),
             "csm_slot_release": ([P, I], I),
             "csm_slot_read": ([P, I, P, I, ctypes.POINTER(I), ctypes.POINTER(ctypes.c_uint8)], I),
-            "csm_prefix_save": ([P, I, I, ctypes.POINTER(I)], I),
+            "csm_slot_set_sampling": ([P, I, ctypes.POINTER(CsmSampling)], I),
+            "csm_prefix_save":([P, I, I, ctypes.POINTER(I)], I),
             "csm_prefix_load": ([P, I, P, P], I),
             "csm_prefix_free": ([P, I], I),
             "csm_prefix_info": ([P, I, ctypes.POINTER(I), ctypes.POINTER(I64)], I),

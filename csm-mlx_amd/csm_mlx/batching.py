@@ -46,11 +46,13 @@ class StreamChunk(NamedTuple):
 
 class _EngineSlots:
     """The engine's side of a ``SlotBatch``: one ``FrameCache`` (csm_begin, the sampler filters, the c0
-    processors, the superseded check, the prefix calls) plus the three slot calls.  ``SlotBatch`` only talks to these
-    methods, so its scheduling is testable against a stub with the same ones."""
+    processors, the superseded check, the prefix calls) plus the slot calls.  ``SlotBatch`` only talks to these
+    methods, so its scheduling is testable against a stub with the same ones (``set_sampling`` only for a job
+    that brings its own sampler or processors: a stub without it serves every other queue)."""
 
     def __init__(self, model: CSM, slots: int, sampler: Sampler, processors):
         self.model = model
+        self.processors = processors
         self.cache = FrameCache(model, slots, sampler, np.zeros(slots, np.uint64), processors)
         self._call = self.cache._call
 
@@ -59,6 +61,26 @@ class _EngineSlots:
 
     def release(self, b: int):
         self._call("csm_slot_release", b)
+
+    def set_sampling(self, b: int, sampler: Optional[Sampler], processors):
+        """Slot b's utterance samples with ``sampler`` and the ``device_processors`` pair ``processors``
+        instead of the batch's (csm_slot_set_sampling); None for either: the batch's.  Right after
+        ``restart(b)``."""
+        base, (bias, pen) = self.cache.sampler, self.processors or (None, None)
+        smp = base if sampler is None else sampler
+        if processors is not None:
+            bias, pen = processors
+        idx = np.asarray(bias.indices if bias else (), np.int64)
+        val = np.ascontiguousarray(bias.values if bias else (), np.float32)
+        V = self.model.n_audio_vocab
+        if idx.size and (idx.min() < 0 or idx.max() >= V):                       # no silent clamp
+            raise ValueError(f"logit_bias index outside [0, {V}): {idx.min()} .. {idx.max()}")
+        idx = np.ascontiguousarray(idx, np.int32)
+        s = _lib.CsmSampling(smp.temp, smp.top_k, smp.top_p, smp.min_p, smp.min_tokens_to_keep, len(idx),
+                             idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                             val.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                             pen.penalty if pen else 0.0, pen.context_size if pen else 0)
+        self._call("csm_slot_set_sampling", b, ctypes.byref(s))
 
     def prefill(self, items: Sequence[Tuple[int, np.ndarray, np.ndarray]]):
         self.cache.prefill_batch(items)
@@ -104,11 +126,12 @@ class _EngineSlots:
 
 
 class _Job:
-    __slots__ = ("ticket", "tokens", "mask", "cap", "seed", "ran", "prefix", "keep_rows")
+    __slots__ = ("ticket", "tokens", "mask", "cap", "seed", "ran", "prefix", "keep_rows", "sampling")
 
-    def __init__(self, ticket, tokens, mask, cap, seed, prefix=None, keep_rows=0):
+    def __init__(self, ticket, tokens, mask, cap, seed, prefix=None, keep_rows=0, sampling=None):
         self.ticket, self.tokens, self.mask, self.cap, self.seed, self.ran = ticket, tokens, mask, cap, seed, 0
         self.prefix, self.keep_rows = prefix, keep_rows
+        self.sampling = sampling      # (sampler or None, device_processors pair or None) of an override; else None
 
 
 class SlotBatch:
@@ -134,14 +157,7 @@ class SlotBatch:
             raise ValueError("a SlotBatch needs at least one slot")
         if chunk < 1:
             raise ValueError("chunk must be >= 1")
-        if isinstance(sampler, HostSampler) or not isinstance(sampler, Sampler):
-            raise ValueError("SlotBatch samples on the GPU: pass a csm_mlx.sampling.Sampler (a host sampler "
-                             "callable pauses every frame for the host and has nothing to batch)")
-        on_device = device_processors(logits_processors, sampler)
-        if logits_processors and on_device is None:
-            raise ValueError("SlotBatch runs logits processors on the GPU only: at most one logit_bias followed "
-                             "by at most one repetition_penalty (make_logits_processors); other lists pause "
-                             "every frame for the host")
+        on_device = self._on_device(sampler, logits_processors)
         self.model = model
         self.slots = slots
         self.chunk = chunk
@@ -154,10 +170,30 @@ class SlotBatch:
         self._tickets = 0
         self._kept: dict = {}            # ticket -> ContextPrefix (None until its utterance has joined)
 
+    @staticmethod
+    def _on_device(sampler, logits_processors):
+        """The ``device_processors`` pair of a sampler and a processor list the GPU can run (None: no
+        processors), for the batch or for one utterance; ``ValueError`` for anything that needs the host."""
+        if isinstance(sampler, HostSampler) or not isinstance(sampler, Sampler):
+            raise ValueError("SlotBatch samples on the GPU: pass a csm_mlx.sampling.Sampler (a host sampler "
+                             "callable pauses every frame for the host and has nothing to batch)")
+        on_device = device_processors(logits_processors, sampler)
+        if logits_processors and on_device is None:
+            raise ValueError("SlotBatch runs logits processors on the GPU only: at most one logit_bias followed "
+                             "by at most one repetition_penalty (make_logits_processors); other lists pause "
+                             "every frame for the host")
+        return on_device
+
     def submit(self, tokens, mask, max_audio_frames: int, seed: int = 0, *, prefix: Optional[ContextPrefix] = None,
-               keep_rows: int = 0) -> int:
+               keep_rows: int = 0, sampler: Optional[Sampler] = None,
+               logits_processors: Optional[List[Callable]] = None) -> int:
         """Queue one utterance: prompt (L, K+1) tokens / mask, at most ``max_audio_frames`` frames, its
         sampling seed.  Returns the ticket ``run`` yields its codes under.
+
+        ``sampler`` / ``logits_processors``: this utterance's own, as the reference's ``generate()`` takes them
+        per call; None (each on its own) means the batch's, an empty processor list means none.  Both run on
+        the GPU under the constructor's rules (``ValueError`` otherwise).  The utterance's codes are those it
+        gets alone with these parameters, whatever its neighbours sample with (csm_slot_set_sampling).
 
         ``prefix``: a ``ContextPrefix`` the prompt begins with; ``tokens`` / ``mask`` are then only the rows
         that follow it (at least one).  Its K / V are copied into the slot when the utterance joins, and only
@@ -183,9 +219,16 @@ class SlotBatch:
         if cap > self.max_frames:     # the engine would refuse the frames that take it there (CSM_ERR_STATE)
             raise _lib.CsmHipError(_lib.CSM_ERR_STATE, f"an utterance of up to {cap} frames does not fit the engine's "
                                    f"{self.max_frames}-frame code history (CSM(..., max_frames=))")
+        sampling = None
+        if sampler is not None or logits_processors is not None:
+            pair = self._on_device(Sampler() if sampler is None else sampler, logits_processors)
+            V = self.model.n_audio_vocab
+            if pair and pair[0] and not all(0 <= i < V for i in pair[0].indices):    # not at the join, mid-run
+                raise ValueError(f"logit_bias index outside [0, {V}): {pair[0].indices}")
+            sampling = (sampler, None if logits_processors is None else (pair or (None, None)))
         ticket = self._tickets
         self._tickets += 1
-        self._queue.append(_Job(ticket, tokens, mask, cap, seed, prefix, keep_rows if cap > 0 else 0))
+        self._queue.append(_Job(ticket, tokens, mask, cap, seed, prefix, keep_rows if cap > 0 else 0, sampling))
         if keep_rows and cap > 0:
             self._kept[ticket] = None
         return ticket
@@ -214,6 +257,8 @@ class SlotBatch:
             if self._queue:
                 job = self._queue.popleft()
                 self._eng.restart(b, job.seed)
+                if job.sampling is not None:        # (a restart puts the slot back on the batch's)
+                    self._eng.set_sampling(b, *job.sampling)
                 self._active[b] = job
                 self._parked[b] = False
                 joins.append((b, job.tokens, job.mask))
@@ -340,9 +385,10 @@ class SlotBatch:
 
 
 def _queued(model, prompts, max_audio_length_ms, slots, temperature, top_k, sampler, seeds, max_audio_frames,
-            logits_processors, chunk, prefixes=None) -> Tuple[SlotBatch, List[int]]:
+            logits_processors, chunk, prefixes=None, samplers=None, prompt_processors=None
+            ) -> Tuple[SlotBatch, List[int]]:
     """What both queue entry points begin with: a ``SlotBatch`` with every prompt submitted under its frame
-    cap, seed and prefix.  Returns (batch, the tickets in prompt order)."""
+    cap, seed, prefix and its own sampler / processors.  Returns (batch, the tickets in prompt order)."""
     smp = _resolve_sampler(temperature, sampler, top_k)
     n = len(prompts)
     caps = [int(max_audio_length_ms / 80)] * n if max_audio_frames is None else [int(c) for c in max_audio_frames]
@@ -352,23 +398,35 @@ def _queued(model, prompts, max_audio_length_ms, slots, temperature, top_k, samp
         prefixes = [None] * n
     if len(prefixes) != n:
         raise ValueError("need one prefix (or None) per prompt")
+    if samplers is None:
+        samplers = [None] * n
+    if len(samplers) != n:
+        raise ValueError("need one sampler (or None) per prompt")
+    if prompt_processors is None:
+        prompt_processors = [None] * n
+    if len(prompt_processors) != n:
+        raise ValueError("need one logits processor list (or None) per prompt")
     seed_list = _seed_list(seeds, n)
     batch = SlotBatch(model, slots, sampler=smp, logits_processors=logits_processors, chunk=chunk)
-    return batch, [batch.submit(t, m, caps[i], int(seed_list[i]), prefix=prefixes[i]) for i, (t, m) in enumerate(prompts)]
+    return batch, [batch.submit(t, m, caps[i], int(seed_list[i]), prefix=prefixes[i], sampler=samplers[i],
+                                logits_processors=prompt_processors[i]) for i, (t, m) in enumerate(prompts)]
 
 
 def generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.ndarray]], max_audio_length_ms: float = 10_000,
                    *, slots: int, temperature: float = 0.0, top_k: int = 0, sampler=None, seeds=None,
                    max_audio_frames: Optional[Sequence[int]] = None, decode: bool = True, with_codes: bool = False,
                    logits_processors: Optional[List[Callable]] = None, chunk: int = DEFAULT_CHUNK,
-                   prefixes: Optional[Sequence[Optional[ContextPrefix]]] = None):
+                   prefixes: Optional[Sequence[Optional[ContextPrefix]]] = None,
+                   samplers: Optional[Sequence[Optional[Sampler]]] = None,
+                   prompt_processors: Optional[Sequence[Optional[List[Callable]]]] = None):
     """``generate_batch`` for any number of prompts through ``slots`` slots: list of waveforms in prompt
     order (or codes if decode=False; (codes, waveforms) with ``with_codes``).  ``max_audio_frames``: one
     frame cap per prompt (default: ``max_audio_length_ms`` for all).  Seeds follow ``generate_batch``: a
     scalar s gives s + i for prompt i.  ``prefixes``: one ``ContextPrefix`` (or None) per prompt, which then
-    holds only the rows after it (``SlotBatch.submit``)."""
+    holds only the rows after it (``SlotBatch.submit``).  ``samplers`` / ``prompt_processors``: one
+    ``Sampler`` / one processor list (or None: the batch's ``sampler`` / ``logits_processors``) per prompt."""
     batch, tickets = _queued(model, prompts, max_audio_length_ms, slots, temperature, top_k, sampler, seeds,
-                             max_audio_frames, logits_processors, chunk, prefixes)
+                             max_audio_frames, logits_processors, chunk, prefixes, samplers, prompt_processors)
     got = dict(batch.run())
     codes = [got[t] for t in tickets]
     if not decode:
@@ -386,14 +444,17 @@ def stream_generate_queue(model: CSM, prompts: Sequence[Tuple[np.ndarray, np.nda
                           max_audio_length_ms: float = 10_000, *, slots: int, temperature: float = 0.0,
                           top_k: int = 0, sampler=None, seeds=None, max_audio_frames: Optional[Sequence[int]] = None,
                           logits_processors: Optional[List[Callable]] = None, chunk: int = DEFAULT_CHUNK,
-                          prefixes: Optional[Sequence[Optional[ContextPrefix]]] = None
+                          prefixes: Optional[Sequence[Optional[ContextPrefix]]] = None,
+                          samplers: Optional[Sequence[Optional[Sampler]]] = None,
+                          prompt_processors: Optional[Sequence[Optional[List[Callable]]]] = None
                           ) -> Generator[Tuple[int, np.ndarray, bool], None, None]:
     """``generate_queue`` as a stream: yields ``(prompt index, pcm, final)`` while the queue runs -- ``pcm``
     the new (v * 1920,) float32 samples of that prompt's utterance (v >= 0), ``final`` on its last event.  The
     concatenation per prompt is what ``stream_generate`` yields for it alone.  The registered audio tokenizer
-    needs ``max_batch >= slots`` and ``max_frames >=`` the largest frame cap."""
+    needs ``max_batch >= slots`` and ``max_frames >=`` the largest frame cap.  ``samplers`` /
+    ``prompt_processors``: per prompt, as in ``generate_queue``."""
     batch, tickets = _queued(model, prompts, max_audio_length_ms, slots, temperature, top_k, sampler, seeds,
-                             max_audio_frames, logits_processors, chunk, prefixes)
+                             max_audio_frames, logits_processors, chunk, prefixes, samplers, prompt_processors)
     index = {t: i for i, t in enumerate(tickets)}
     for ev in batch.stream():
         yield index[ev.ticket], ev.pcm, ev.final

@@ -2,7 +2,7 @@
 //   csm_engine.hip          frame paths: the block stacks, path selection, body / head enqueue, graph capture
 //   csm_engine_weights.hip  lifecycle and weights: create / destroy, loader, quantizer, derived tables
 //   csm_engine_abi.hip      frame ABI: csm_begin, prefill, csm_run_frames*, csm_frame_*, csm_read_codes
-//   csm_engine_slots.hip    continuous batching: csm_slot_restart / csm_slot_release / csm_slot_read
+//   csm_engine_slots.hip    continuous batching: csm_slot_restart / csm_slot_release / csm_slot_read / csm_slot_set_sampling
 //   csm_engine_prefix.hip   shared context prefixes: csm_prefix_save / csm_prefix_load / csm_prefix_free / csm_prefix_info
 //   csm_engine_lab.hip      lab and inspection: csm_bench_*, debug taps, csm_linear, csm_kv_read, csm_set_option
 #pragma once
@@ -193,6 +193,16 @@ struct csm_engine {
   bool slot_mode = false;     // from the first slot call after csm_begin until the next csm_begin
   std::vector<char> parked_host;
   std::vector<int> slot_first;
+  // Per-utterance sampling (csm_slot_set_sampling): slot_sampling[b] is what slot b's utterance samples with
+  // and slot_bias[b] its dense logit bias.  The kernels read them (per_slot: their table pointers are set)
+  // from the first override after csm_begin on; until then the scalars above serve the whole batch and the
+  // frame runs exactly as without this.  A slot with no override holds the batch's values (batch_sampling);
+  // samp_own[b] marks one that has its own, samp_host mirrors the device rows for the plan (frame_plan).
+  SlotSampling* slot_sampling = nullptr;  // [B_max]
+  float* slot_bias = nullptr;             // [B_max][Vpad]
+  bool per_slot = false;
+  std::vector<SlotSampling> samp_host;
+  std::vector<char> samp_own;
   // Shared context prefixes (csm_engine_prefix.hip): saved backbone K / V rows of a prompt's first positions,
   // each in a hipMalloc of its own (not in batch_allocs: a growing batch keeps them), by handle.  A prefix is
   // valid for the weights and RoPE table it was computed with: weights_epoch counts every change of either
@@ -216,6 +226,7 @@ struct csm_engine {
   int g_B = -1;
   float g_temp = -1.f;
   int g_topk = -1;
+  int g_plan = -1;  // FramePlan::key() the graphs were captured for
   std::vector<void*> allocs;
   std::vector<void*> batch_allocs;
   std::vector<int> pos_host;
@@ -333,6 +344,22 @@ enum class HeadPhase {
                // p + its head (logits stored); piece K feeds the last code and advances the frame.  The c0
                // head ran as C0Logits (csm_frame_c0_logits).
 };
+
+// The plan class of a frame: which of the head's paths the whole batch takes.  Without per-slot sampling it
+// restates the batch's sampler and processors; with it, it is the union of what the slots holding an
+// utterance need -- any non-greedy slot: a sampled plan; any with top-p / min-p: the filtered kernel for all
+// rows; any with a bias or penalty: the processors pass.  The per-slot values themselves are read from the
+// table at run time, so only a change of key() captures the frame graph again.
+struct FramePlan {
+  bool sampled, filtered, processors, per_slot;
+  int key() const { return (sampled ? 1 : 0) | (filtered ? 2 : 0) | (processors ? 4 : 0) | (per_slot ? 8 : 0); }
+};
+FramePlan frame_plan(const csm_engine* e);
+// the batch's sampler and processors (csm_begin / csm_set_*) as a table row
+SlotSampling batch_sampling(const csm_engine* e);
+// csm_engine_slots.hip: per-slot operation, after the batch's values changed -- the rows of the slots without
+// an override follow (no-op otherwise)
+void refresh_slot_sampling(csm_engine* e);
 
 // csm_engine_weights.hip
 void ensure_batch(csm_engine* e, int B);

@@ -322,6 +322,7 @@ void launch_xsd(csm_engine* e, int M, int i, const unsigned long long* part_prev
     if (sample) {
       a.sample = 1; a.s_top_k = e->top_k; a.s_K = e->K; a.s_cb = i; a.s_temperature = e->temperature;
       a.s_seeds = e->seeds; a.s_slot_frame = e->slot_frame;
+      a.s_slots = e->per_slot ? e->slot_sampling : nullptr;
     }
   }
   launch_dec_step_xs(a, st, e->wdt == WDT_Q4);
@@ -404,6 +405,32 @@ StepPlan plan_step(csm_engine* e, int i, bool fuse_sample) {
 
 }  // namespace
 
+SlotSampling batch_sampling(const csm_engine* e) {
+  SlotSampling s{};
+  s.temperature = e->temperature; s.top_k = e->top_k;
+  s.use_top_p = e->use_top_p; s.use_min_p = e->use_min_p; s.min_keep = e->min_keep;
+  s.top_p_cut = e->top_p_cut; s.log_min_p = e->log_min_p;
+  s.penalty = e->c0_penalty; s.context = e->c0_context; s.bias = e->c0_bias_on ? 1 : 0;
+  return s;
+}
+
+FramePlan frame_plan(const csm_engine* e) {
+  FramePlan f{};
+  f.per_slot = e->per_slot;
+  auto need = [&f](const SlotSampling& s) {
+    f.sampled |= s.temperature > 0.f;
+    f.filtered |= s.temperature > 0.f && (s.use_top_p || s.use_min_p);
+    f.processors |= s.bias != 0 || s.penalty > 0.f;
+  };
+  if (!e->per_slot) {
+    need(batch_sampling(e));
+    return f;
+  }
+  for (int b = 0; b < e->B; ++b)
+    if (!e->parked_host[b]) need(e->samp_own[b] ? e->samp_host[b] : batch_sampling(e));
+  return f;
+}
+
 void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piece) {
   if (phase == HeadPhase::Frame && dec_frame_eligible(e)) {
     enqueue_dec_frame_only(e, st);
@@ -411,13 +438,16 @@ void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piec
     return;
   }
   const int B = e->B, K = e->K, D = e->D, Dd = e->Dd, V = e->V, Vp = e->Vpad;
+  const FramePlan fp = frame_plan(e);
+  const SlotSampling* slots = fp.per_slot ? e->slot_sampling : nullptr;  // the kernels read row b's values from it
   const bool host_codes = phase == HeadPhase::Forced || phase == HeadPhase::HostPiece;  // fed forward from e->force
-  const bool greedy = e->temperature <= 0.f && !host_codes;
+  const bool greedy = !fp.sampled && !host_codes;
   // the frame's own logits processors (csm_set_c0_processors) transform the stored c0 logits before c0 is picked
-  const bool c0_proc = phase == HeadPhase::Frame && e->c0_processors();
+  const bool c0_proc = phase == HeadPhase::Frame && fp.processors;
   const bool c0_sampled = !greedy || phase == HeadPhase::FromHostC0 || c0_proc;  // c0 published by sample_kernel as a single partial
   // sampled frames (top-k only): the persistent step's launch can run the sampler too
-  const bool fuse_sample = !greedy && (phase == HeadPhase::Frame || phase == HeadPhase::FromHostC0) && !e->use_top_p && !e->use_min_p;
+  const bool fuse_sample = !greedy && (phase == HeadPhase::Frame || phase == HeadPhase::FromHostC0) &&
+                           (fp.per_slot ? !fp.filtered : !e->use_top_p && !e->use_min_p);
   const int n0 = head_blocks(Vp, D, B, e->wdt);        // c0-head blocks (partials per row)
   const int ni = head_blocks(Vp, Dd, B, e->head_wdt);  // ci-head blocks
   auto part = [&](int cb) { return e->part + (size_t)cb * e->B_max * e->part_stride; };
@@ -426,6 +456,7 @@ void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piec
   sp.slot_frame = e->slot_frame; sp.K = K; sp.codes = e->codes; sp.part_stride = e->part_stride;
   sp.use_top_p = e->use_top_p; sp.use_min_p = e->use_min_p; sp.min_keep = e->min_keep;
   sp.top_p_cut = e->top_p_cut; sp.log_min_p = e->log_min_p;
+  sp.slots = slots; sp.slots_filtered = fp.filtered ? 1 : 0;
   sp.forced = host_codes ? e->force : nullptr;
   // c0 = codebook0_head(h_last) (generation.py:42); greedy arg-max fused into the GEMV epilogue
   GemvParams g = gp(e);
@@ -439,6 +470,7 @@ void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piec
     cp.logits = e->c0_logits; cp.ls = Vp; cp.V = V; cp.bias = e->c0_bias_on ? e->c0_bias : nullptr; cp.penalty = e->c0_penalty;
     cp.context = e->c0_context; cp.hist = e->hist; cp.B = B; cp.K = K; cp.F_cap = e->F_cap;
     cp.frame_ctr = e->frame_ctr; cp.slot_frame = e->slot_frame;
+    cp.slots = slots; cp.slot_bias = e->slot_bias;
     launch_c0_process(cp, st);
   }
   const bool pieces = phase == HeadPhase::HostPiece;

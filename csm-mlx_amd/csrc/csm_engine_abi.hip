@@ -79,6 +79,9 @@ int csm_begin(csm_engine* e, int B, const uint64_t* seeds, float temperature, in
     e->slot_mode = false;
     e->parked_host.assign(B, 0);
     e->slot_first.assign(B, 0);
+    e->per_slot = false;
+    e->samp_own.assign(B, 0);
+    e->samp_host.assign(B, SlotSampling{});
     std::vector<uint64_t> s(B, 0);
     if (seeds) memcpy(s.data(), seeds, B * 8);
     HIPCHK(hipMemcpyAsync(e->seeds, s.data(), B * 8, hipMemcpyHostToDevice, e->st));
@@ -107,6 +110,7 @@ int csm_set_sampler_filters(csm_engine* e, double top_p, double min_p, int min_t
     e->log_min_p = e->use_min_p ? (float)std::log(min_p) : 0.f;
     e->min_keep = min_tokens_to_keep;
     ++e->filters_id;
+    refresh_slot_sampling(e);
   }
   CSM_CATCH
 }
@@ -135,6 +139,7 @@ int csm_set_c0_processors(csm_engine* e, int n_bias, const int32_t* bias_idx, co
     e->c0_penalty = repetition_penalty;
     e->c0_context = repetition_penalty > 0.f ? repetition_context_size : 0;
     ++e->filters_id;  // the frame graphs hold these by value: re-capture
+    refresh_slot_sampling(e);
   }
   CSM_CATCH
 }
@@ -280,8 +285,12 @@ int csm_run_frames(csm_engine* e, int nframes, int* all_done) {
       HIPCHK(hipGetLastError());
       nframes = 0;
     }
+    // (per-slot sampling: the slots' values are read from device memory, so a join captures nothing; a
+    // change of the plan class does)
+    const int plan = frame_plan(e).key();
     if (use_graph && (e->g_B != e->B || e->g_temp != e->temperature || e->g_topk != e->top_k ||
-                      e->g_filters != e->filters_id || !e->g_head)) {
+                      e->g_filters != e->filters_id || e->g_plan != plan || !e->g_head)) {
+      if (e->frames_run > 0) HIPCHK(hipStreamSynchronize(e->st));  // frames enqueued without a wait still replay the old graphs
       if (e->g_body) (void)hipGraphExecDestroy(e->g_body);
       if (e->g_head) (void)hipGraphExecDestroy(e->g_head);
       e->g_body = capture(e, enqueue_body);
@@ -290,6 +299,7 @@ int csm_run_frames(csm_engine* e, int nframes, int* all_done) {
       e->g_temp = e->temperature;
       e->g_topk = e->top_k;
       e->g_filters = e->filters_id;
+      e->g_plan = plan;
     }
     for (int f = 0; f < nframes; ++f) {
       body_if_needed(e, true);

@@ -6,6 +6,11 @@
 // restart rewrites that state with one small kernel on the engine stream and no graph is captured again.
 // The code history stays [F_cap][B][K] but is written as a ring over the global frame index; slot b's
 // utterance occupies the rows from slot_first[b] on.
+//
+// Per-utterance sampling (csm_slot_set_sampling): the sampler's and the c0 processors' parameters of slot b are
+// row b of a device table the sample kernels, the persistent step's sampler and c0_process_kernel read at run
+// time, written on the engine stream like the rest of a slot's state, so frames already enqueued never see a
+// later write and a join captures nothing; csm_engine.hip frame_plan picks the frame's plan class from the rows.
 #include "csm_engine.h"
 
 namespace {
@@ -22,6 +27,8 @@ struct SlotResetParams {
   int b, K, D;
   uint64_t seed;
   int park;  // 1: the slot holds no utterance from here on
+  SlotSampling* sampling;  // per-slot operation: the table, whose row b goes back to the batch's values (null: no table in use)
+  SlotSampling batch;
 };
 
 // Slot b starts afresh (park 0) or is parked (park 1).  A parked slot's rows still run in every launch: its
@@ -36,6 +43,7 @@ __global__ __launch_bounds__(256) void slot_reset_kernel(SlotResetParams p) {
     p.parked[b] = p.park ? 1 : 0;
     p.pos[b] = 0;
     p.seeds[b] = p.seed;
+    if (p.sampling) p.sampling[b] = p.batch;
   }
   for (int k = t; k < p.K; k += 256) p.codes[(size_t)b * p.K + k] = 0;
   if (p.park)
@@ -66,6 +74,9 @@ void slot_reset(csm_engine* e, int b, uint64_t seed, bool park) {
   SlotResetParams p{};
   p.done = e->done; p.n_frames = e->n_frames; p.slot_frame = e->slot_frame; p.codes = e->codes; p.parked = e->parked;
   p.pos = e->pos; p.seeds = e->seeds; p.h_last = e->h_last; p.b = b; p.K = e->K; p.D = e->D; p.seed = seed; p.park = park ? 1 : 0;
+  // the slot forgets its utterance's own sampling: the next one starts from the batch's
+  p.sampling = e->per_slot ? e->slot_sampling : nullptr; p.batch = batch_sampling(e);
+  e->samp_own[b] = 0;
   hipLaunchKernelGGL(slot_reset_kernel, dim3(1), dim3(256), 0, e->st, p);
   HIPCHK(hipGetLastError());
   if (body) {
@@ -82,7 +93,52 @@ void slot_reset(csm_engine* e, int b, uint64_t seed, bool park) {
   e->slot_first[b] = e->frames_run;
 }
 
+// One row of the table, by value: ordered on the engine stream behind the frames already enqueued
+__global__ void slot_sampling_set_kernel(SlotSampling* table, int b, SlotSampling row) {
+  if (threadIdx.x == 0) table[b] = row;
+}
+
+// The whole table from the host's view of it: the rows of the slots with an override, the batch's for the rest
+void upload_slot_sampling(csm_engine* e) {
+  std::vector<SlotSampling> rows(e->B);
+  for (int b = 0; b < e->B; ++b) rows[b] = e->samp_own[b] ? e->samp_host[b] : batch_sampling(e);
+  HIPCHK(hipMemcpyAsync(e->slot_sampling, rows.data(), rows.size() * sizeof(SlotSampling), hipMemcpyHostToDevice, e->st));
+  HIPCHK(hipStreamSynchronize(e->st));  // (the host rows are released on return)
+}
+
+// csm_sampling -> a table row, with the value checks of csm_set_sampler_filters and csm_set_c0_processors
+SlotSampling checked_row(csm_engine* e, const csm_sampling& s) {
+  if (!(s.temperature >= 0.f)) throw CsmError(CSM_ERR_ARG, "temperature must be >= 0");
+  if (!(s.top_p >= 0.0 && s.top_p <= 1.0) || !(s.min_p >= 0.0 && s.min_p <= 1.0) || s.min_tokens_to_keep < 1)
+    throw CsmError(CSM_ERR_ARG, "top_p and min_p must lie in [0, 1], min_tokens_to_keep >= 1");
+  if (s.n_bias < 0 || (s.n_bias > 0 && (!s.bias_idx || !s.bias_val))) throw CsmError(CSM_ERR_ARG, "bad logit_bias arguments");
+  for (int i = 0; i < s.n_bias; ++i)
+    if (s.bias_idx[i] < 0 || s.bias_idx[i] >= e->V)
+      throw CsmError(CSM_ERR_ARG, "logit_bias index " + std::to_string(s.bias_idx[i]) + " outside [0, " + std::to_string(e->V) + ")");
+  if (!(s.repetition_penalty >= 0.f)) throw CsmError(CSM_ERR_ARG, "repetition_penalty must be >= 0");
+  if (s.repetition_context_size < 0 || s.repetition_context_size > C0_WINDOW_MAX)
+    throw CsmError(CSM_ERR_ARG, "repetition_context_size must lie in [0, " + std::to_string(C0_WINDOW_MAX) + "]");
+  SlotSampling r{};
+  r.temperature = s.temperature; r.top_k = s.top_k;
+  // (the cuts as csm_set_sampler_filters rounds them; a greedy utterance has no filter chain)
+  r.use_top_p = s.temperature > 0.f && s.top_p > 0.0 && s.top_p < 1.0;
+  r.use_min_p = s.temperature > 0.f && s.min_p != 0.0;
+  r.top_p_cut = (float)(1.0 - s.top_p);
+  r.log_min_p = r.use_min_p ? (float)std::log(s.min_p) : 0.f;
+  r.min_keep = s.min_tokens_to_keep;
+  r.penalty = s.repetition_penalty;
+  r.context = s.repetition_penalty > 0.f ? s.repetition_context_size : 0;
+  r.bias = s.n_bias > 0 ? 2 : 0;
+  return r;
+}
+
 }  // namespace
+
+void refresh_slot_sampling(csm_engine* e) {
+  if (!e->per_slot) return;
+  HIPCHK(hipSetDevice(e->dev));
+  upload_slot_sampling(e);
+}
 
 extern "C" {
 
@@ -93,6 +149,37 @@ int csm_slot_restart(csm_engine* e, int b, uint64_t seed) {
 
 int csm_slot_release(csm_engine* e, int b) {
   CSM_TRY { slot_reset(e, b, 0, true); }
+  CSM_CATCH
+}
+
+int csm_slot_set_sampling(csm_engine* e, int b, const csm_sampling* s) {
+  CSM_TRY {
+    if (!e) throw CsmError(CSM_ERR_ARG, "null engine");
+    if (e->B <= 0 || !e->slot_mode) throw CsmError(CSM_ERR_STATE, "csm_slot_set_sampling outside slot mode: csm_slot_restart first");
+    if (b < 0) throw CsmError(CSM_ERR_ARG, "slot index out of range");
+    if (b >= e->B) throw CsmError(CSM_ERR_STATE, "slot " + std::to_string(b) + " beyond the batch of " + std::to_string(e->B));
+    if (e->c0_pending) throw CsmError(CSM_ERR_STATE, "csm_frame_finish pending");
+    if (e->parked_host[b]) throw CsmError(CSM_ERR_STATE, "slot " + std::to_string(b) + " holds no utterance: csm_slot_restart first");
+    if (e->frames_run > e->slot_first[b])
+      throw CsmError(CSM_ERR_STATE, "slot " + std::to_string(b) + ": its utterance has already run a frame");
+    const SlotSampling row = s ? checked_row(e, *s) : batch_sampling(e);
+    HIPCHK(hipSetDevice(e->dev));
+    if (s && s->n_bias > 0) {  // the slot's dense bias row, zero where unset (a repeated index: the last value)
+      std::vector<float> dense(e->Vpad, 0.f);
+      for (int i = 0; i < s->n_bias; ++i) dense[s->bias_idx[i]] = s->bias_val[i];
+      HIPCHK(hipMemcpyAsync(e->slot_bias + (size_t)b * e->Vpad, dense.data(), dense.size() * 4, hipMemcpyHostToDevice, e->st));
+      HIPCHK(hipStreamSynchronize(e->st));
+    }
+    e->samp_own[b] = s ? 1 : 0;
+    e->samp_host[b] = row;
+    if (s && !e->per_slot) {  // the first override of this batch: every slot's row, the batch's for the others
+      e->per_slot = true;
+      upload_slot_sampling(e);
+    } else if (e->per_slot) {
+      hipLaunchKernelGGL(slot_sampling_set_kernel, dim3(1), dim3(64), 0, e->st, e->slot_sampling, b, row);
+      HIPCHK(hipGetLastError());
+    }
+  }
   CSM_CATCH
 }
 

@@ -71,6 +71,8 @@ void ensure_batch(csm_engine* e, int B) {
   e->n_frames = (int*)e->balloc(Bm * 4);
   e->slot_frame = (int*)e->balloc(Bm * 4);
   e->parked = (uint8_t*)e->balloc(Bm);
+  e->slot_sampling = (SlotSampling*)e->balloc(Bm * sizeof(SlotSampling));
+  e->slot_bias = (float*)e->balloc(Bm * Vp * 4);
   e->done = (uint8_t*)e->balloc(Bm);
   e->seeds = (uint64_t*)e->balloc(Bm * 8);
   // partial slots per row: enough for any head tiling (c0 / ci heads, dense or q4; >= Vp/2 blocks never occur)

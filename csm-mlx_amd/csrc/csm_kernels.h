@@ -250,6 +250,20 @@ struct AttnParams {
   int blk;  // ATTN_FRAMES: rows per frame (the codec's downsample_stride)
 };
 
+// One row of the per-slot sampling table (csm_slot_set_sampling, csm_engine_slots.hip): what slot b's
+// utterance samples with when the batch runs per-slot -- the fields SampleParams and C0ProcessParams carry
+// as scalars for the whole batch.  Every kernel that reads it handles one row per workgroup, so a row's
+// values are block-uniform.
+struct SlotSampling {
+  float temperature;  // 0: greedy -- the first max of the raw logits, no noise, 1 / temperature never taken
+  int top_k;
+  int use_top_p, use_min_p, min_keep;
+  float top_p_cut, log_min_p;
+  float penalty;      // 0: no repetition penalty
+  int context;
+  int bias;           // 0: none, 1: the batch's dense bias (C0ProcessParams::bias), 2: the slot's own row
+};
+
 struct SampleParams {
   const float* logits;  // [B][ls]
   int ls, V;            // V = number of valid logits
@@ -267,6 +281,11 @@ struct SampleParams {
   // (float32(log(min_p))) and the first min_keep ranks
   int use_top_p, use_min_p, min_keep;
   float top_p_cut, log_min_p;
+  // per-slot operation: row b's temperature, top_k and filters come from slots[b] instead of the scalars above
+  // (null: the scalars).  slots_filtered: some slot holding an utterance has a filter on, so every row runs
+  // sample_filtered_kernel (what the scalars decide otherwise)
+  const SlotSampling* slots;
+  int slots_filtered;
 };
 
 // mlx_lm make_logits_processors on the c0 logits, run inside the frame (csm_set_c0_processors; c0_process.h
@@ -284,6 +303,10 @@ struct C0ProcessParams {
   int B, K, F_cap;
   const int* frame_ctr;   // the global frame index (where the history is written)
   const int* slot_frame;  // [B] each utterance's own frame index (how much of the history is its own)
+  // per-slot operation: row b's penalty, context and bias (SlotSampling::bias; its own row: slot_bias[b])
+  // come from slots[b] (null: the scalars above)
+  const SlotSampling* slots;
+  const float* slot_bias;  // [B_max][ls]
 };
 void launch_c0_process(const C0ProcessParams& p, hipStream_t st);
 
@@ -514,6 +537,7 @@ struct DecStepXsArgs {
   float s_temperature;
   const uint64_t* s_seeds;
   const int* s_slot_frame;  // [M] each row's own frame index
+  const SlotSampling* s_slots;  // per-slot operation: row m's temperature and top_k (null: the two scalars)
   float* qkvp;                            // bf16 XSD_QSPLIT: [2][RMAX][QKV] the QKV K halves' partial sums, then [48][RMAX] row scales
 };
 constexpr int DEC_XSD_STAMPS = 64;

@@ -975,7 +975,10 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
     }
     return;
   }
-  if (p.temperature <= 0.f) {
+  // (per-slot operation: row b's own values, block-uniform)
+  const float temperature = row_temperature(p.slots, b, p.temperature);
+  const int top_k = row_top_k(p.slots, b, p.top_k);
+  if (temperature <= 0.f) {
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int v = tid; v < V; v += 256) {
@@ -994,10 +997,10 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
       const int v = tid + 256 * i;
       lv[i] = v < V ? lg[v] : 0.f;
     }
-    const bool topk = p.top_k > 0 && p.top_k < V;
-    const float thr = topk ? topk_threshold<256, SAMPLE_NPT>(tid, V, p.top_k, hist, wsum, sh, RegSlots<SAMPLE_NPT>{lv}) : -INFINITY;
+    const bool topk = top_k > 0 && top_k < V;
+    const float thr = topk ? topk_threshold<256, SAMPLE_NPT>(tid, V, top_k, hist, wsum, sh, RegSlots<SAMPLE_NPT>{lv}) : -INFINITY;
     const uint64_t key = gumbel_key(p.seeds[b], p.slot_frame[b] * p.K + p.cb);
-    const float inv_t = 1.0f / p.temperature;
+    const float inv_t = 1.0f / temperature;
     double best = -INFINITY;
     int bi = 0x7fffffff;
     // With a top-k threshold the kept entries (k plus ties, ~2 % of the row) are compacted into LDS
@@ -1091,8 +1094,28 @@ __global__ __launch_bounds__(256) void sample_filtered_kernel(SampleParams p) {
     lgs[v] = lv[i];
     keep[v] = 0;
   }
+  // per-slot operation: row b's own values (block-uniform, read once); the filter chain is on for the
+  // whole batch as soon as one slot has a filter, so a row may come with both off -- it then keeps the top-k
+  // set alone and picks sample_kernel's code -- or greedy
+  const SlotSampling* row = p.slots ? p.slots + b : nullptr;
+  const float temperature = row ? row->temperature : p.temperature;
+  const int top_k = row ? row->top_k : p.top_k;
+  const bool use_top_p = row ? row->use_top_p : p.use_top_p, use_min_p = row ? row->use_min_p : p.use_min_p;
+  const int min_keep = row ? row->min_keep : p.min_keep;
+  const float top_p_cut = row ? row->top_p_cut : p.top_p_cut, log_min_p = row ? row->log_min_p : p.log_min_p;
+  if (temperature <= 0.f) {  // a greedy row: the first max of the raw logits, before any barrier
+    double gb;
+    int gi;
+    greedy_pass<256, SAMPLE_NPT>(tid, V, RegSlots<SAMPLE_NPT>{lv}, gb, gi);
+    const int code = clamp_code(block_argmax<double, 4>(tid, gb, gi, sdv, si), V);
+    if (tid == 0) {
+      p.codes[(size_t)b * p.K + p.cb] = code;
+      if (p.part) p.part[(size_t)b * p.part_stride] = pack_argmax(0.f, code);
+    }
+    return;
+  }
   const float thr =
-      (p.top_k > 0 && p.top_k < V) ? topk_threshold<256, SAMPLE_NPT>(tid, V, p.top_k, hist, wsum, sh, RegSlots<SAMPLE_NPT>{lv}) : -INFINITY;
+      (top_k > 0 && top_k < V) ? topk_threshold<256, SAMPLE_NPT>(tid, V, top_k, hist, wsum, sh, RegSlots<SAMPLE_NPT>{lv}) : -INFINITY;
   // lse = max + log(sum exp(l - max)) over the valid logits (per-thread sums in i order, waves by
   // DPP reductions, the 4 waves in order)
   float mx = -INFINITY;
@@ -1141,7 +1164,7 @@ __global__ __launch_bounds__(256) void sample_filtered_kernel(SampleParams p) {
     lpv[r] = l - lse;
     kp[r] = valid && l >= thr;
   }
-  if (p.use_top_p) {
+  if (use_top_p) {
     // cum_asc at sorted position r = sum of exp(lp) of kept entries at positions >= r
     float suf[SAMPLE_NPT];
     float acc = 0.f;
@@ -1164,9 +1187,9 @@ __global__ __launch_bounds__(256) void sample_filtered_kernel(SampleParams p) {
     float later = c - acc;          // threads after tid in this wave
     for (int w2 = 3; w2 > wave; --w2) later += fred[w2];
 #pragma unroll
-    for (int r = 0; r < SAMPLE_NPT; ++r) kp[r] = kp[r] && (suf[r] + later > p.top_p_cut);
+    for (int r = 0; r < SAMPLE_NPT; ++r) kp[r] = kp[r] && (suf[r] + later > top_p_cut);
   }
-  if (p.use_min_p) {
+  if (use_min_p) {
     // the best kept lp, a block max over the kept entries (oracle filter_keep: lp[keep].max()).  Not
     // simply sorted position 0: top_k keeps by the raw logit while the sort is by the fp32-rounded
     // lp = l - lse with index-ascending ties, so a dropped entry can sort ahead of a kept one.
@@ -1178,16 +1201,16 @@ __global__ __launch_bounds__(256) void sample_filtered_kernel(SampleParams p) {
     __syncthreads();
     if (lane == 0) fred[wave] = bm;
     __syncthreads();
-    const float tmin = fmaxf(fmaxf(fred[0], fred[1]), fmaxf(fred[2], fred[3])) + p.log_min_p;
+    const float tmin = fmaxf(fmaxf(fred[0], fred[1]), fmaxf(fred[2], fred[3])) + log_min_p;
 #pragma unroll
-    for (int r = 0; r < SAMPLE_NPT; ++r) kp[r] = kp[r] && (!(lpv[r] < tmin) || SAMPLE_NPT * tid + r < p.min_keep);
+    for (int r = 0; r < SAMPLE_NPT; ++r) kp[r] = kp[r] && (!(lpv[r] < tmin) || SAMPLE_NPT * tid + r < min_keep);
   }
 #pragma unroll
   for (int r = 0; r < SAMPLE_NPT; ++r)
     if (kp[r]) keep[idx[r]] = 1;
   __syncthreads();
   const uint64_t key = gumbel_key(p.seeds[b], p.slot_frame[b] * p.K + p.cb);
-  const float inv_t = 1.0f / p.temperature;
+  const float inv_t = 1.0f / temperature;
   double best = -INFINITY;
   int bi = 0x7fffffff;
   float bl = -INFINITY;
@@ -1205,7 +1228,7 @@ __global__ __launch_bounds__(256) void sample_filtered_kernel(SampleParams p) {
     }
   }
   int code = block_argmax<double, 4>(tid, best, bi, sdv, si);
-  if (code == 0x7fffffff) {
+  if (code == 0x7fffffff && (use_top_p || use_min_p)) {  // (no filter on: sample_kernel's clamp below)
     __syncthreads();
     code = block_argmax<float, 4>(tid, bl, bli, fred, si);
   }
@@ -1260,11 +1283,17 @@ __global__ void advance_kernel(AdvanceParams p) {
 __global__ __launch_bounds__(256) void c0_process_kernel(C0ProcessParams p) {
   __shared__ int win[C0_WINDOW_MAX];
   const int b = blockIdx.x, f = p.frame_ctr[0];
-  const int n = c0_window_n(min(p.slot_frame[b], f), p.context, p.penalty);  // never a predecessor's codes in the same slot
+  // per-slot operation: row b's own penalty, window and bias (block-uniform, read once); a row with none of
+  // them passes through unchanged
+  const SlotSampling* row = p.slots ? p.slots + b : nullptr;
+  const float penalty = row ? row->penalty : p.penalty;
+  const int context = row ? row->context : p.context;
+  const float* bias = !row ? p.bias : row->bias == 2 ? p.slot_bias + (size_t)b * p.ls : row->bias == 1 ? p.bias : nullptr;
+  const int n = c0_window_n(min(p.slot_frame[b], f), context, penalty);  // never a predecessor's codes in the same slot
   for (int j = threadIdx.x; j < n; j += 256) win[j] = c0_window_code_ring(p.hist, f, j, b, p.B, p.K, p.F_cap);
   __syncthreads();
   float* lg = p.logits + (size_t)b * p.ls;
-  for (int v = threadIdx.x; v < p.V; v += 256) lg[v] = c0_processed(lg[v], v, p.bias, win, n, p.penalty);
+  for (int v = threadIdx.x; v < p.V; v += 256) lg[v] = c0_processed(lg[v], v, bias, win, n, penalty);
 }
 
 // ============================================================================ launchers
@@ -1438,7 +1467,7 @@ void launch_sample(const SampleParams& p, int wdt, int B, hipStream_t st) {
     fprintf(stderr, "csm: sampler supports V <= %d (got %d)\n", 256 * SAMPLE_NPT, p.V);
     abort();
   }
-  if (!p.forced && p.temperature > 0.f && (p.use_top_p || p.use_min_p)) {
+  if (!p.forced && (p.slots ? p.slots_filtered != 0 : p.temperature > 0.f && (p.use_top_p || p.use_min_p))) {
     hipLaunchKernelGGL(sample_filtered_kernel, dim3(B), dim3(256), 0, st, p);
     return;
   }

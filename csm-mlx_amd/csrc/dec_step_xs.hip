@@ -762,13 +762,18 @@ __device__ __forceinline__ void role_s(Ctx& c) {
   static_assert(sizeof(sampler::Scratch<NWV>) <= sizeof(Lds::red), "the sampler borrows L.red");
   const DecStepXsArgs& p = c.p;
   const int m = c.w, V = p.n_valid;
+  // (per-slot operation: row m's own temperature and top-k, uniform over the workgroup; a greedy row draws
+  // no noise and takes the first max of the raw logits)
+  const float temperature = sampler::row_temperature(p.s_slots, m, p.s_temperature);
+  const int top_k = sampler::row_top_k(p.s_slots, m, p.s_top_k);
+  const bool greedy = temperature <= 0.f;
   // the Gumbel noise does not depend on the logits: drawn before the wait
   const uint64_t key = gumbel_key(p.s_seeds[m], p.s_slot_frame[m] * p.s_K + p.s_cb);
   double gn[NPT];
 #pragma unroll
   for (int i = 0; i < NPT; ++i) {
     const int v = c.tid + NT * i;
-    gn[i] = v < V ? gumbel_noise(key, v) : 0.0;
+    gn[i] = v < V && !greedy ? gumbel_noise(key, v) : 0.0;
   }
   const int fs0 = CW_FS + 64 * (m >> 5);  // the head tiles of the row's row tile
   wait_words(c, p.head_tiles, [fs0](int i) { return fs0 + i; }, c.ep + 1u);
@@ -782,10 +787,11 @@ __device__ __forceinline__ void role_s(Ctx& c) {
   sampler::Scratch<NWV>& S = *reinterpret_cast<sampler::Scratch<NWV>*>(&c.L.red[0][0][0][0]);
   const sampler::RegSlots<NPT> logit{lg};
   float thr = -INFINITY;
-  if (p.s_top_k > 0 && p.s_top_k < V) thr = sampler::topk_threshold<NT, NPT>(c.tid, V, p.s_top_k, S.hist, S.wsum, S.sh, logit);
+  if (!greedy && top_k > 0 && top_k < V) thr = sampler::topk_threshold<NT, NPT>(c.tid, V, top_k, S.hist, S.wsum, S.sh, logit);
   double best;
   int bi;
-  sampler::gumbel_pass<NT, NPT>(c.tid, V, thr, 1.0f / p.s_temperature, logit, [&](int i, int) { return gn[i]; }, best, bi);
+  // (greedy: sampler::greedy_pass's arguments -- no threshold, scale 1, the zero noise above)
+  sampler::gumbel_pass<NT, NPT>(c.tid, V, thr, greedy ? 1.0f : 1.0f / temperature, logit, [&](int i, int) { return gn[i]; }, best, bi);
   const int code = sampler::clamp_code(sampler::block_argmax<double, NWV>(c.tid, best, bi, S.bv, S.bi), V);
   if (c.tid == 0) {
     p.codes[(size_t)m * p.codes_K + p.s_cb] = code;

@@ -145,4 +145,19 @@ __device__ __forceinline__ void gumbel_pass(int tid, int V, float thr, float inv
   }
 }
 
+// A greedy row (temperature 0): this thread's candidate for the first max of the raw logits -- the Gumbel
+// pass with no threshold, the scale 1 (l * 1.0f is l) and no noise drawn, so 1 / temperature is never taken.
+// -> block_argmax<double>, which picks what sample_kernel's greedy branch picks.
+template <int NT, int NPT, typename Logit>
+__device__ __forceinline__ void greedy_pass(int tid, int V, Logit&& logit, double& best, int& bi) {
+  gumbel_pass<NT, NPT>(tid, V, -INFINITY, 1.0f, logit, [](int, int) { return 0.0; }, best, bi);
+}
+
+// Row b's temperature / top_k in per-slot operation (slots non-null: csm_kernels.h SlotSampling), else the
+// launch's scalars.  b is the workgroup's row, so the result is block-uniform: read once, ahead of the loops.
+__device__ __forceinline__ float row_temperature(const SlotSampling* slots, int b, float temperature) {
+  return slots ? slots[b].temperature : temperature;
+}
+__device__ __forceinline__ int row_top_k(const SlotSampling* slots, int b, int top_k) { return slots ? slots[b].top_k : top_k; }
+
 }  // namespace sampler

@@ -166,6 +166,8 @@ int csm_read_codes(csm_engine* e, int32_t* hist, int32_t* n_frames, uint8_t* don
  *                     every frame but touch nothing outside the slot.
  *   csm_slot_read     codes [n][K] of slot b's utterance (EOS excluded; cap_frames = rows the buffer holds,
  *                     CSM_ERR_ARG when it is too small), *n_frames and *done; any pointer may be NULL.
+ *   csm_slot_set_sampling  slot b's utterance has a sampler and processors of its own (below); every
+ *                     csm_slot_restart and csm_slot_release puts the slot back on the batch's.
  * CSM_ERR_STATE: b >= B; a restart between csm_frame_c0_logits and csm_frame_finish; running frames while a
  * restarted slot has no prompt; frames that would take an utterance past max_frames;
  * csm_read_codes(hist != NULL), csm_frame_c0_logits and csm_frame_forced in slot mode (csm_read_codes still
@@ -173,6 +175,23 @@ int csm_read_codes(csm_engine* e, int32_t* hist, int32_t* n_frames, uint8_t* don
 int csm_slot_restart(csm_engine* e, int b, uint64_t seed);
 int csm_slot_release(csm_engine* e, int b);
 int csm_slot_read(csm_engine* e, int b, int32_t* codes, int cap_frames, int* n_frames, uint8_t* done);
+/* The sampler and the c0 processors of one utterance: csm_begin's temperature and top_k, csm_set_sampler_filters'
+ * top_p, min_p and min_tokens_to_keep, csm_set_c0_processors' bias, penalty and context, with their meanings
+ * (temperature 0: greedy, and then no filter; n_bias 0: no bias; repetition_penalty 0: none). */
+typedef struct csm_sampling {
+  float temperature; int top_k; double top_p, min_p; int min_tokens_to_keep;
+  int n_bias; const int32_t* bias_idx; const float* bias_val;
+  float repetition_penalty; int repetition_context_size;
+} csm_sampling;
+/* Slot b's utterance samples with *s instead of the batch's sampler and processors (s NULL: the batch's
+ * again).  After csm_slot_restart(b), before the first frame of that utterance.  The values live in device
+ * memory, written on the engine stream: frames already enqueued do not see them, and a join captures no
+ * graph -- only a change of what the slots holding an utterance need between them does (all greedy / some
+ * sampled / some with top_p or min_p / some with a bias or penalty: one frame graph each).  A greedy utterance
+ * beside sampled ones gets the codes it gets in a greedy batch.  CSM_ERR_ARG as csm_set_sampler_filters and
+ * csm_set_c0_processors (a bias index outside [0, n_audio_vocab), a penalty < 0, a context above 256, ...);
+ * CSM_ERR_STATE for b >= B, outside slot mode, for a parked slot, or once the utterance has run a frame. */
+int csm_slot_set_sampling(csm_engine* e, int b, const csm_sampling* s);
 /* Shared context prefixes (no reference counterpart: the reference's generate() pushes every context segment
  * through the backbone again for each sentence, generation.py:108-125).  Attention is causal, so the backbone
  * K / V of a prompt's first P rows depend on those rows alone: they are saved once and loaded into any

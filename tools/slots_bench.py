@@ -14,7 +14,10 @@ the engine ran that were useful.  usage: slots_bench.py [repeats]
   (c) SlotBatch.stream at chunk 1, 2, 4, 8  PCM per utterance while the queue runs (mimi_202407, synthetic weights)
 with, for (c), the time from an utterance's join to its first PCM event (median, p95; without streaming it is
 the time to the utterance's end, printed beside it) and the codec's kernel launches per decoded chunk
-(the host counter behind mimi_debug_read "launches")."""
+(the host counter behind mimi_debug_read "launches").
+
+``slots_bench.py --sampling [repeats]``: the queue at chunk 8 greedy, sampled (0.8 / top-k 50) and with the two
+alternating per prompt (``generate_queue(samplers=)``), with the median and spread of each."""
 import ctypes
 import os
 import sys
@@ -31,8 +34,8 @@ from csm_mlx.tokenizers import tokenize_text_segment  # noqa: E402
 from csm_mlx.weights import bf16_bits, synthetic_csm_weights  # noqa: E402
 
 N, SLOTS = 96, 32
-STREAM = "--stream" in sys.argv
-argv = [a for a in sys.argv[1:] if a != "--stream"]
+STREAM, SAMPLING = "--stream" in sys.argv, "--sampling" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--stream", "--sampling")]
 repeats = int(argv[0]) if argv else 2
 args = csm_1b()
 model = CSM(args, dtype="bf16", max_batch=SLOTS)
@@ -159,8 +162,36 @@ def stream_bench():
                   f"{note}", flush=True)
 
 
+def sampling_bench():
+    """The queue at chunk 8 with a greedy batch, a sampled one (0.8 / top-k 50) and a greedy batch whose odd
+    prompts bring that sampler along (``samplers=``: per-slot operation, the sampled plan), alternating.  A
+    library without csm_slot_set_sampling (CSM_HIP_LIB: a build of the parent commit) runs the first two."""
+    from csm_mlx.sampling import Sampler
+    hot = Sampler(0.8, 50)
+    cases = [("greedy", {}), ("sampled 0.8 / top-k 50", {"sampler": hot})]
+    if hasattr(_lib.lib(), "csm_slot_set_sampling"):
+        cases.append(("greedy + 0.8 / top-k 50 alternating", {"samplers": [hot if i % 2 else None for i in range(N)]}))
+    for _, kw in cases:                            # warm-up: graphs, tables
+        generate_queue(model, prompts[:SLOTS], slots=SLOTS, max_audio_frames=[4] * SLOTS, decode=False, seeds=0,
+                       **({"samplers": kw["samplers"][:SLOTS]} if "samplers" in kw else kw))
+    rates = {name: [] for name, _ in cases}
+    for r in range(repeats):
+        for name, kw in cases:
+            t = time.perf_counter()
+            codes = generate_queue(model, prompts, slots=SLOTS, max_audio_frames=caps, decode=False, chunk=8, seeds=0, **kw)
+            dt = time.perf_counter() - t
+            assert [len(c) for c in codes] == caps
+            rates[name].append(useful / dt)
+            print(f"{name:40s} run {r}: {useful / dt:8.1f} useful frames/s  {dt:6.3f} s", flush=True)
+    for name, v in rates.items():
+        print(f"{name:40s} median {np.median(v):8.1f}  min {min(v):8.1f}  max {max(v):8.1f}  n = {len(v)}", flush=True)
+
+
 if STREAM:
     stream_bench()
+    sys.exit(0)
+if SAMPLING:
+    sampling_bench()
     sys.exit(0)
 
 generate_queue(model, prompts[:SLOTS], slots=SLOTS, max_audio_frames=[4] * SLOTS, decode=False)   # warm-up: graphs, tables
