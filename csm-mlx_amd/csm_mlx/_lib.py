@@ -141,6 +141,7 @@ def lib():
             "mimi_lab_conv1d": ([P, I, P, I64, P, I64, P, P, I64, P, P, I64], I),
             "mimi_lab_convtr": ([P, I, P, I64, P, I64, P, P, I64], I),
             "mimi_lab_linear": ([P, I, P, I64, P, I64, P, P, I64], I),
+            "mimi_lab_layernorm": ([I, I, P, P, P, F, P, I64], I),
             "mimi_lab_rvq_encode": ([I, I, I, I, I, I, I, I, P, P, P, P], I),
         }
         for name, (args, res) in sig.items():

@@ -220,6 +220,20 @@ int mimi_lab_linear(const int* geo, int n_geo, const float* x, int64_t x_n, cons
   CSM_CATCH
 }
 
+int mimi_lab_layernorm(int M, int D, const float* x, const float* w, const float* b, float eps, float* out, int64_t out_n) {
+  CSM_TRY {
+    need(x && w && b && out, "layernorm: x, w, b and out are required");
+    need(M > 0 && M <= (1 << 20) && D > 0 && D <= (1 << 20) && (int64_t)M * D <= LAB_MAX, "layernorm shape");
+    need(out_n >= (int64_t)M * D && out_n <= LAB_MAX, "layernorm: out is smaller than M x D");
+    LabStream s;
+    LabBuf dx(x, (size_t)M * D * 4), dw(w, (size_t)D * 4), db(b, (size_t)D * 4), dout(out, (size_t)out_n * 4);
+    launch_layernorm_rows(dx.f(), D, dw.f(), db.f(), eps, dout.f(), M, s.st);
+    finish(s.st);
+    HIPCHK(hipMemcpy(out, dout.p, (size_t)out_n * 4, hipMemcpyDeviceToHost));
+  }
+  CSM_CATCH
+}
+
 int mimi_lab_rvq_encode(int gemm, int M, int T, int cd, int bins, int n_q, int k0, int k1, const float* cb,
                         const float* c2half, float* r, int32_t* codes) {
   CSM_TRY {

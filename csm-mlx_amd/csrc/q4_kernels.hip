@@ -211,7 +211,10 @@ void launch_embed_q4(const EmbedParams& p, int n_text_rows, int M, hipStream_t s
 
 // ============================================================================ quantized GEMV
 // y[m, n] = sum_k norm(x)[m, k] * w_hat[n, k],  w_hat = s_g * q + b_g  (QuantizedLinear, transpose=True)
-// evaluated per half group of 32 as  s_g * sum(q * x) + b_g * sum(x).
+// evaluated per half group of 32 as  s_g * sum((q - 8) * x) + (b_g + 8 s_g) * sum(x): the nibbles centred, so
+// that the two terms do not cancel (b_g is the group's minimum, about -7.5 s_g; with q in 0..15 each term is
+// two to three times the result and so is the rounding error: 2.3 x the plain form's on tiny at M = 1 once the
+// norm weights are not all ones, 0.9 x centred -- DESIGN.md section 2.1).
 //
 // A 256-thread block owns RPB = (256/G)*RPT rows; a group of G threads covers K in KS steps of
 // G*32 elements, each lane one 16-B load (32 nibbles = half a group) per row and step plus the
@@ -327,14 +330,14 @@ __global__ __launch_bounds__(256) void gemv_q4_kernel(GemvParams p) {
         for (int w = 0; w < 4; ++w) {
           const uint32_t u = wq[s][r][w];
           const uint32_t lo = u & 0x0F0F0F0Fu, hi = (u >> 4) & 0x0F0F0F0Fu;
-          qf[r][w * 8 + 0] = (float)((lo >> 0) & 0xFFu);
-          qf[r][w * 8 + 1] = (float)((hi >> 0) & 0xFFu);
-          qf[r][w * 8 + 2] = (float)((lo >> 8) & 0xFFu);
-          qf[r][w * 8 + 3] = (float)((hi >> 8) & 0xFFu);
-          qf[r][w * 8 + 4] = (float)((lo >> 16) & 0xFFu);
-          qf[r][w * 8 + 5] = (float)((hi >> 16) & 0xFFu);
-          qf[r][w * 8 + 6] = (float)((lo >> 24) & 0xFFu);
-          qf[r][w * 8 + 7] = (float)((hi >> 24) & 0xFFu);
+          qf[r][w * 8 + 0] = (float)((lo >> 0) & 0xFFu) - 8.f;
+          qf[r][w * 8 + 1] = (float)((hi >> 0) & 0xFFu) - 8.f;
+          qf[r][w * 8 + 2] = (float)((lo >> 8) & 0xFFu) - 8.f;
+          qf[r][w * 8 + 3] = (float)((hi >> 8) & 0xFFu) - 8.f;
+          qf[r][w * 8 + 4] = (float)((lo >> 16) & 0xFFu) - 8.f;
+          qf[r][w * 8 + 5] = (float)((hi >> 16) & 0xFFu) - 8.f;
+          qf[r][w * 8 + 6] = (float)((lo >> 24) & 0xFFu) - 8.f;
+          qf[r][w * 8 + 7] = (float)((hi >> 24) & 0xFFu) - 8.f;
         }
       }
 #pragma unroll
@@ -359,7 +362,8 @@ __global__ __launch_bounds__(256) void gemv_q4_kernel(GemvParams p) {
               d3 = fmaf(qf[r][j + 3], xv[j + 3], d3);
             }
             const float dq = (d0 + d1) + (d2 + d3);
-            acc[i][r] = fmaf(bf16_lo(sb[s][r]), dq, fmaf(bf16_hi(sb[s][r]), hsum, acc[i][r]));
+            const float sg = bf16_lo(sb[s][r]);
+            acc[i][r] = fmaf(sg, dq, fmaf(fmaf(8.f, sg, bf16_hi(sb[s][r])), hsum, acc[i][r]));
           }
         }
       }

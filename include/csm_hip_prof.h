@@ -114,6 +114,9 @@ int mimi_lab_convtr(const int* geo, int n_geo, const float* x, int64_t x_n, cons
 /* W [N][K]; scale [N] optional (epi add). */
 int mimi_lab_linear(const int* geo, int n_geo, const float* x, int64_t x_n, const float* W, int64_t w_n,
                     const float* scale, float* out, int64_t out_n);
+/* LayerNorm of rows x [M][D] with w [D], b [D] (layernorm_rows_kernel); out [>= M * D] in / out. */
+int mimi_lab_layernorm(int M, int D, const float* x, const float* w, const float* b, float eps, float* out,
+                       int64_t out_n);
 /* RVQ encode of rows r [M][cd] (in / out: the final residual) over codebooks [k0, k1) of cb [n_q][bins][cd]
  * with c2half [n_q][bins]; codes [M / T][n_q][T] in / out.  gemm = 0: the block-per-row kernel, 1: the
  * distance GEMM (cd % 32 == 0, cd <= 256, bins % 256 == 0). */

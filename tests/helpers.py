@@ -1,6 +1,7 @@
 """Shared builders for the parity tests (test infrastructure)."""
 import dataclasses
 import functools
+import zlib
 
 import numpy as np
 
@@ -36,6 +37,7 @@ _QUANT = {}
 
 def _quant_for(weights):
     from oracle.quant_oracle import quantize_weights
+    weights = _RIG_BASE.get(id(weights), weights)                    # a norm rig quantizes nothing anew
     if id(weights) not in _QUANT:
         _QUANT[id(weights)] = quantize_weights(weights)
     return _QUANT[id(weights)]
@@ -50,7 +52,14 @@ def _oracle_for(args, weights, bf16, q4, f64=False):
         if q4:
             w.update(_quant_for(weights))                            # (packed, scales, biases): exact in float64
         return OracleCSM(args, w, *cfg, dtype=np.float64)
-    w = {k: bf16_round(v) for k, v in weights.items()} if bf16 else weights
+    base = _RIG_BASE.get(id(weights))
+    if base is not None:                                             # norm_rig: the base dict's conversions, its own norms
+        w = dict(oracle_for(args, base, bf16, q4).w)
+        w.update({k: v for k, v in weights.items() if is_norm(k)})
+        return OracleCSM(args, w, *cfg)
+    # the engine keeps RMSNorm weights as given (fp32 in, fp32 kept: DESIGN.md "RMSNorm weights fp32"), so the
+    # bf16 variant rounds every tensor but those
+    w = {k: v if is_norm(k) else bf16_round(v) for k, v in weights.items()} if bf16 else weights
     if q4:
         w = quantize_dequantize_weights(weights, quant=_quant_for(weights))
         w["audio_head"] = bf16_round(weights["audio_head"])
@@ -269,6 +278,99 @@ def eos_weights(args_key="1b", seed=0):
     return args, eos_rig(args, w)
 
 
+# ----------------------------------------------------------------------------- norms that are not all ones
+def is_norm(name):
+    """A CSM RMSNorm weight: input_layernorm / post_attention_layernorm of a layer, or a stack's final norm."""
+    return name.endswith("norm.weight")
+
+
+def _rig_rng(seed, name):
+    return np.random.default_rng([seed, zlib.crc32(name.encode())])
+
+
+def _pow2(rng, shape, lo, hi, negate=0.0):
+    """2^U(lo, hi) per element, a fraction ``negate`` of them negated."""
+    v = np.exp2(rng.uniform(lo, hi, shape))
+    return (v * np.where(rng.random(shape) < negate, -1.0, 1.0)).astype(np.float32)
+
+
+_RIG_BASE = {}          # id(rigged dict) -> the dict it was made from (kept alive by _NORM_RIGS)
+_NORM_RIGS = {}
+
+
+def norm_rig(args, w, seed=0):
+    """Seeded weights whose RMSNorm weights can be told apart (test infrastructure): every norm tensor of ``w``
+    (``is_norm``) gets its own draw, keyed by (seed, name): magnitude 2^U(-2, 2) per element, about 10 % of the
+    elements negated.  With the synthetic all-ones norms n1[l], n1[l + 1], n2[l] and the final norm are
+    interchangeable and sum(x * nw) = sum(x); with these a norm weight that is skipped, applied twice, taken
+    from another layer, read at an offset or left stale moves the taps by 1e5 x the bar
+    (tests/test_norm_rig_cpu.py).  Nothing else changes.  Returns a new dict, memoised per (dict, seed) so that
+    ``oracle_for``'s cache holds; ``oracle_for`` reuses ``w``'s bf16 / int4 conversions for every other tensor."""
+    key = (id(w), seed)
+    if key not in _NORM_RIGS:
+        out = dict(w)
+        for name, v in w.items():
+            if is_norm(name):
+                out[name] = _pow2(_rig_rng(seed, name), v.shape, -2, 2, 0.1)
+        _RIG_BASE[id(out)] = w
+        _NORM_RIGS[key] = out
+    return _NORM_RIGS[key]
+
+
+def norm_weights(args_key, seed=0):
+    """(args, norm_rig of the ``csm_weights`` dict)."""
+    args, w = csm_weights(args_key)
+    return args, norm_rig(args, w, seed)
+
+
+MIMI_CLAMP = 1e-5       # EuclideanCodebook: embedding_sum / max(cluster_usage, 1e-5)
+
+
+def mimi_clamped_bins(m, q, k, seed=0):
+    """The two bins of codebook (q, k) that ``mimi_affine_rig`` puts under the clamp (usage 0, usage 1e-6)."""
+    name = f"quantizer.{q}.vq.layers.{k}._codebook.clamped"
+    return _rig_rng(seed, name).choice(m.bins, 2, replace=False)
+
+
+def mimi_place_clamped(m, codes, seed=0):
+    """``codes`` (B >= 2, n_q, F >= 2) with each codebook's two clamped bins placed once: utterance 0 frame 0 and
+    the last utterance's frame 1.  Returns a copy."""
+    codes = np.array(codes, np.int32)
+    for k in range(m.n_q):
+        lo = mimi_clamped_bins(m, "rvq_first" if k == 0 else "rvq_rest", 0 if k == 0 else k - 1, seed)
+        codes[0, k, 0], codes[-1, k, 1] = lo
+    return codes
+
+
+def mimi_affine_rig(m, w, seed=0):
+    """Seeded Mimi weights whose LayerNorm affine terms, layer scales and cluster usages can be told apart:
+      * norm1/2.weight = 2^U(-1, 1), about 10 % negated;  norm1/2.bias = 0.5 N(0, 1);
+      * layer_scale_1/2.scale = m.layer_scale x 2^U(-2, 2) per channel, separate draws for 1 and 2;
+      * cluster_usage = 2^U(-2, 2) with the embedding_sum row multiplied by the same factor (the effective rows
+        keep their scale); per codebook two bins (``mimi_clamped_bins``) sit under the clamp, usage 0 and 1e-6,
+        their embedding_sum rows scaled by 1e-5 so that sum / 1e-5 stays O(0.1).
+    Returns a new dict."""
+    out = dict(w)
+    for name, v in w.items():
+        rng = _rig_rng(seed, name)
+        if name.endswith((".norm1.weight", ".norm2.weight")):
+            out[name] = _pow2(rng, v.shape, -1, 1, 0.1)
+        elif name.endswith((".norm1.bias", ".norm2.bias")):
+            out[name] = (0.5 * rng.standard_normal(v.shape)).astype(np.float32)
+        elif name.endswith((".layer_scale_1.scale", ".layer_scale_2.scale")):
+            out[name] = (np.float32(m.layer_scale) * _pow2(rng, v.shape, -2, 2)).astype(np.float32)
+        elif name.endswith("._codebook.cluster_usage"):
+            p = name[:-len(".cluster_usage")]
+            q, k = p.split(".")[1], int(p.split(".")[4])
+            f = _pow2(rng, v.shape, -2, 2)
+            rows = (np.asarray(w[p + ".embedding_sum"], np.float32) * f[:, None]).astype(np.float32)
+            lo = mimi_clamped_bins(m, q, k, seed)
+            f[lo] = (0.0, 1e-6)
+            rows[lo] = (np.asarray(w[p + ".embedding_sum"], np.float32)[lo] * np.float32(MIMI_CLAMP)).astype(np.float32)
+            out[name], out[p + ".embedding_sum"] = f, rows
+    return out
+
+
 # ----------------------------------------------------------------------------- float64 taps: errors and the bar
 TAPS = ("h_last", "c0", "ci")
 # bar = BAR_MARGIN x e32.  Two float32 evaluations of the same arithmetic with different blocking and exp / rsqrt
@@ -309,15 +411,18 @@ def f64_reference(args, weights, variant, prompts, codes, block=None):
 MIMI_BAR_MARGIN = BAR_MARGIN
 
 
-def mimi_pair(name, mode):
-    """(MimiArgs, synthetic weights, float32 oracle, float64 oracle) of a codec config, memoised."""
-    key = ("mimi", name, mode)
+def mimi_pair(name, mode, rig=None):
+    """(MimiArgs, synthetic weights, float32 oracle, float64 oracle) of a codec config, memoised.
+    rig: a function (m, w) -> new weights applied to the synthetic ones (``mimi_affine_rig``)."""
+    key = ("mimi", name, mode, rig)
     if key not in _ORACLES:
         from csm_mlx.config import MIMI_CONFIGURATION
         from csm_mlx.weights import synthetic_mimi_weights
         from oracle.mimi_oracle import OracleMimi
         m = dataclasses.replace(MIMI_CONFIGURATION[name], attn_mode=mode)
         w = synthetic_mimi_weights(m)
+        if rig is not None:
+            w = rig(m, w)
         _ORACLES[key] = (m, w, OracleMimi(m, w), OracleMimi(m, w, dtype=np.float64))
     return _ORACLES[key]
 

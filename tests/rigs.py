@@ -132,14 +132,17 @@ def codes_per_utterance(model, prompts, frames, sampler, seeds=None, logits_proc
 
 
 # ----------------------------------------------------------------------------- the codec beside its oracle
-def mimi_codec(name, mode, max_batch, max_frames):
-    """(MimiArgs, MimiCodec with synthetic weights, float32 OracleMimi on the same weights)."""
+def mimi_codec(name, mode, max_batch, max_frames, rig=None):
+    """(MimiArgs, MimiCodec with synthetic weights, float32 OracleMimi on the same weights).
+    rig: a function (m, w) -> new weights applied to the synthetic ones (helpers.mimi_affine_rig)."""
     from csm_mlx.config import MIMI_CONFIGURATION
     from csm_mlx.mimi import MimiCodec
     from csm_mlx.weights import synthetic_mimi_weights
     from oracle.mimi_oracle import OracleMimi
     m = dataclasses.replace(MIMI_CONFIGURATION[name], attn_mode=mode)
     w = synthetic_mimi_weights(m)
+    if rig is not None:
+        w = rig(m, w)
     codec = MimiCodec(m, max_batch=max_batch, max_frames=max_frames)
     codec.load_weights(w)
     return m, codec, OracleMimi(m, w)

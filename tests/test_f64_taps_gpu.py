@@ -21,7 +21,7 @@ import dataclasses
 import numpy as np
 import pytest
 
-from helpers import BAR_MARGIN, TAPS, csm_weights, f64_reference, prompt_ids, tap_errors, tiny_prompt_ids
+from helpers import BAR_MARGIN, TAPS, csm_weights, f64_reference, norm_rig, prompt_ids, tap_errors, tiny_prompt_ids
 from rigs import TAP_NAMES, build_model, epoch, frame_taps, handoffs, set_option, synchronize
 
 pytestmark = pytest.mark.gpu
@@ -38,9 +38,15 @@ _W = {}
 
 
 def _weights(key):
+    """key: "tiny", "1b", "tiny_f1280", or one of them + "+norm": the same weights through helpers.norm_rig
+    (tests/test_norm_rig_gpu.py runs this module's procedure on those)."""
+    if key.endswith("+norm"):
+        args, w = _weights(key[:-len("+norm")])
+        return args, norm_rig(args, w)
     if key in ("tiny", "1b"):
         return csm_weights(key)
     if key not in _W:                                                       # tiny_f1280: the K = 1280 stage case
+        assert key == "tiny_f1280", key                                     # (any other key is registered in _W)
         from csm_mlx.models import csm_tiny
         from csm_mlx.weights import synthetic_csm_weights
         args = dataclasses.replace(csm_tiny(), decoder_name=key)
@@ -84,17 +90,18 @@ def _run(model, prompts, forced=None):
 _REFS = {}
 
 
-def _reference(key, dtype, prompts, codes):
-    """Memoised by (model, dtype, prompts, codes): the paths of one engine at one B produce the same codes."""
+def _reference(key, dtype, prompts, codes, block=None):
+    """Memoised by (model, dtype, prompts, codes): the paths of one engine at one B produce the same codes.
+    block: helpers.oracle_taps' (a prompt-sized prefill reaches the oracles in pieces)."""
     variant = {"float32": "fp32"}.get(dtype, dtype)
     k = (key, variant, tuple(t.tobytes() for t, _ in prompts), codes.tobytes())
     if k not in _REFS:
         args, w = _weights(key)
-        _REFS[k] = f64_reference(args, w, variant, prompts, codes)
+        _REFS[k] = f64_reference(args, w, variant, prompts, codes, block)
     return _REFS[k]
 
 
-def _check(key, dtype, model, prompts, options=(), forced=None, expect=None, capsys=None):
+def _check(key, dtype, model, prompts, options=(), forced=None, expect=None, capsys=None, block=None):
     """Run the case with ``options`` (name -> 0) switched off, compare every tap with the float64 oracle
     forced on the engine's codes, hold the epoch deltas to ``expect``."""
     for name in options:
@@ -115,7 +122,7 @@ def _check(key, dtype, model, prompts, options=(), forced=None, expect=None, cap
     else:                                                                    # first-index arg-max of its own logits
         assert np.array_equal(codes[:, :, 0], got[1].argmax(-1)), "c0 is not the arg-max of the engine's c0 logits"
         assert np.array_equal(codes[:, :, 1:], got[2].argmax(-1)), "a code is not the arg-max of its ci logits row"
-    t64, e32 = _reference(key, dtype, prompts, codes)
+    t64, e32 = _reference(key, dtype, prompts, codes, block)
     err = tap_errors(got, t64)
     ci = err["ci"]
     split = {"h_last": err["h_last"].max(), "c0": err["c0"].max(), "ci1": ci[:, :, 0].max(), "ci2+": ci[:, :, 1:].max()}
@@ -171,13 +178,9 @@ def test_1b_batched(dtype, B, off, engine_1b_bf16, engine_1b_q4, capsys):
     _check("1b", dtype, model, _prompts_1b(B), options=off, expect=_expect(K, B, dec_xsd=xsd), capsys=capsys)
 
 
-@pytest.mark.parametrize("B", [2, 32])
-def test_1b_bf16_forced(B, engine_1b_bf16, capsys):
-    """csm_frame_forced: seeded random codes in [0, 2048) (the codec's bins), with 0 and 2047 placed in every
-    codebook column of some row; the reference is forced on the same codes.  B = 2: GEMV launches; 32: the
-    persistent step."""
-    args, w, model = engine_1b_bf16
-    K, bins = args.n_audio_codebooks, 2048
+def _forced_codes(B, K, bins=2048):
+    """Seeded random codes (FRAMES, B, K) in [0, bins) (the codec's bins), with 0 and bins - 1 placed in every
+    codebook column of some row."""
     rng = np.random.default_rng(50 + B)
     forced = rng.integers(0, bins, (FRAMES, B, K)).astype(np.int32)
     forced[0, 0, :K - 1] = 0                                  # (an all-zero frame would be EOS: the last column's
@@ -185,26 +188,40 @@ def test_1b_bf16_forced(B, engine_1b_bf16, capsys):
     forced[1, B - 1, :] = bins - 1
     assert all((forced[:, :, k] == 0).any() and (forced[:, :, k] == bins - 1).any() for k in range(K))
     assert forced.any(-1).all()
-    _check("1b", "bf16", model, _prompts_1b(B), forced=forced, expect=_expect(K, B, dec_xsd=B >= 8), capsys=capsys)
+    return forced
+
+
+@pytest.mark.parametrize("B", [2, 32])
+def test_1b_bf16_forced(B, engine_1b_bf16, capsys):
+    """csm_frame_forced: seeded random codes in [0, 2048) (the codec's bins), with 0 and 2047 placed in every
+    codebook column of some row; the reference is forced on the same codes.  B = 2: GEMV launches; 32: the
+    persistent step."""
+    args, w, model = engine_1b_bf16
+    K = args.n_audio_codebooks
+    _check("1b", "bf16", model, _prompts_1b(B), forced=_forced_codes(B, K), expect=_expect(K, B, dec_xsd=B >= 8),
+           capsys=capsys)
 
 
 # ----------------------------------------------------------------------------- tiny shapes
+def _tiny_prompts(args, B, seed):
+    from csm_mlx.tokenizers import tokenize_text_segment
+    return [tokenize_text_segment(tiny_prompt_ids(seed + b, 10 + b % 3), 0, args.n_audio_codebooks) for b in range(B)]
+
+
+def _tiny_case(key, dtype, B, seed, capsys):
+    """A fresh engine on ``key``'s weights, B prompts seeded from ``seed``, the module's check."""
+    args, w, model = _engine(key, dtype, B)
+    _check(key, dtype, model, _tiny_prompts(args, B, seed), capsys=capsys)
+    del model
+
+
 @pytest.mark.parametrize("B", [1, 9, 33])
 @pytest.mark.parametrize("dtype", ["float32", "bf16", "q4"])
 def test_tiny(dtype, B, capsys):
-    from csm_mlx.tokenizers import tokenize_text_segment
-    args, w, model = _engine("tiny", dtype, B)
-    prompts = [tokenize_text_segment(tiny_prompt_ids(4000 + 97 * B + b, 10 + b % 3), 0, args.n_audio_codebooks)
-               for b in range(B)]
-    _check("tiny", dtype, model, prompts, capsys=capsys)
-    del model
+    _tiny_case("tiny", dtype, B, 4000 + 97 * B, capsys)
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "q4"])
 def test_tiny_f1280(dtype, capsys):
     """A decoder MLP of width 1280: 20 K-stages of 64, which an 8-wave block does not divide."""
-    from csm_mlx.tokenizers import tokenize_text_segment
-    args, w, model = _engine("tiny_f1280", dtype, 8)
-    prompts = [tokenize_text_segment(tiny_prompt_ids(4800 + b, 10 + b % 3), 0, args.n_audio_codebooks) for b in range(8)]
-    _check("tiny_f1280", dtype, model, prompts, capsys=capsys)
-    del model
+    _tiny_case("tiny_f1280", dtype, 8, 4800, capsys)

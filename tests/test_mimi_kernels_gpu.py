@@ -1,7 +1,7 @@
 """Each Mimi codec kernel, alone, against a float64 evaluation of its own definition.
 
 The operations run through the lab door (csrc/mimi_lab.hip: mimi_lab_conv1d / _convtr / _linear /
-_rvq_encode) on seeded host arrays; mimi_lab_plan reports which kernel, split-K factor and fold the launcher
+_layernorm / _rvq_encode) on seeded host arrays; mimi_lab_plan reports which kernel, split-K factor and fold the launcher
 takes for the geometry -- the launchers' own function, so the coverage asserted here is the coverage run.
 
 Reference: plain float64 numpy of the definitions in csrc/mimi_kernels.h -- the im2col product for the convs,
@@ -397,6 +397,77 @@ def test_linear(c):
     mask = np.ones(out.shape, bool)
     mask[oi.reshape(-1)] = False
     assert np.array_equal(out[mask].view(np.uint32), init[mask].view(np.uint32)), "a store outside the addressed region"
+
+
+# ----------------------------------------------------------------------------- LayerNorm rows
+LN_ROWS, LN_EPS = 300, 1e-5
+LN_CASES = [(D, M) for D in (32, 40, 256, 512) for M in (1, 63, LN_ROWS)]
+
+
+def _ln_data(D):
+    """LN_ROWS rows of three classes (the kernel runs the first M of them), weights and biases some negative:
+    "far": mean 100, std 0.01 (a one-pass E[x^2] - E[x]^2 variance would lose them); "flat": all elements 1.5
+    (variance 0: eps alone; every partial sum of 1.5 is exact in float32, so the mean is too); "plain": the rest."""
+    rng = np.random.default_rng([4, D])
+    x = acts(rng, (LN_ROWS, D)) * rng.uniform(0.1, 4.0, (LN_ROWS, 1)).astype(np.float32)
+    cls = np.array(["plain"] * LN_ROWS, object)
+    cls[3::4], cls[[7, 200]] = "far", "flat"
+    far = cls == "far"
+    x[far] = (100.0 + 0.01 * rng.standard_normal((int(far.sum()), D))).astype(np.float32)
+    x[cls == "flat"] = np.float32(1.5)
+    w = (rng.standard_normal(D) * 0.8).astype(np.float32)
+    b = (rng.standard_normal(D) * 0.5).astype(np.float32)
+    assert (w < 0).any() and (b < 0).any()
+    return x, w, b, cls
+
+
+def _ln_two_pass(x, w, b, dt):
+    x, w, b = x.astype(dt), w.astype(dt), b.astype(dt)
+    mean = x.sum(-1, keepdims=True, dtype=dt) / dt(x.shape[-1])
+    c = x - mean
+    var = (c * c).sum(-1, keepdims=True, dtype=dt) / dt(x.shape[-1])
+    return c * (dt(1) / np.sqrt(var + dt(LN_EPS))) * w + b
+
+
+def _ln_err(y, y64):
+    """Per row: max |y - float64| / the row's largest |float64 value|."""
+    return np.abs(np.asarray(y, F64) - y64).max(-1) / np.abs(y64).max(-1)
+
+
+@pytest.mark.parametrize("D,M", LN_CASES, ids=[f"d{D}_m{M}" for D, M in LN_CASES])
+def test_layernorm(D, M):
+    """layernorm_rows_kernel through mimi_lab_layernorm against a float64 LayerNorm.  D = 32 and 40 leave most of
+    the block's 256 threads without an element, 256 gives each one, 512 two; M = 1, 63, 300 rows (one block a row).
+    Unit: per row, max |got - float64| / the row's largest |float64 value|.  Bar, as test_linear's: 1.5 x the error of
+    a plain float32 two-pass evaluation in numpy (mean, centred squares, one rsqrt) in that unit, measured each run --
+    the margin is ``check``'s, this file's for every element-wise case.  The bar is taken per row class over all
+    LN_ROWS rows of the class the case's rows are drawn from (the largest of one row's D rounding errors is too
+    noisy a statistic for a 1.5 x bar, cf. LIN_CASES' convT note), and a class is held to its own bar: the "far"
+    rows' float32 error is that of a mean rounded at 100 against a spread of 0.01, about 1e4 x the others'.
+    A "flat" row must come out as the bias exactly.  Stores past M x D must not happen."""
+    _lib, L = _L()
+    x, w, b, cls = _ln_data(D)
+    y64 = _ln_two_pass(x, w, b, F64)
+    e32 = _ln_err(_ln_two_pass(x, w, b, np.float32), y64)
+    out = np.full(M * D + 7, SENT, np.float32)
+    xin = np.ascontiguousarray(x[:M])
+    _lib.check(L.mimi_lab_layernorm(M, D, _p(xin), _p(w), _p(b), LN_EPS, _p(out), out.size))
+    assert (out[M * D:].view(np.uint32) == SENT.view(np.uint32)).all(), "a store outside the addressed region"
+    got = out[:M * D].reshape(M, D)
+    err = _ln_err(got, y64[:M])
+    for c in ("plain", "far"):
+        rows = np.flatnonzero(cls[:M] == c)
+        if not rows.size:
+            continue
+        bar = 1.5 * float(e32[cls == c].max())
+        worst = float(err[rows].max())
+        print(f"layernorm d{D}_m{M} {c}: err {worst:.3e} bar {bar:.3e} ratio {worst / bar:.2f}")
+        assert bar > 0
+        assert worst <= bar, f"{c}: {worst:.3e} > {bar:.3e} at row {int(rows[err[rows].argmax()])}"
+    for r in np.flatnonzero(cls[:M] == "flat"):
+        assert np.array_equal(got[r].view(np.uint32), b.view(np.uint32)), f"flat row {r}: (x - mean) is not 0"
+    with pytest.raises(ValueError):
+        _lib.check(L.mimi_lab_layernorm(M, D, _p(xin), _p(w), _p(b), LN_EPS, _p(out), M * D - 1))
 
 
 # ----------------------------------------------------------------------------- RVQ encode

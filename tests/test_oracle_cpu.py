@@ -105,9 +105,11 @@ def test_csm_oracle_golden():
 
 
 # ----------------------------------------------------------------------------- Mimi oracle
-@pytest.mark.parametrize("name", ["tiny", "mimi_202407"])
-def test_mimi_oracle_matches_transformers(name):
-    """Causal mode == the independent transformers MimiModel with mapped weights."""
+@pytest.mark.parametrize("name,rigged", [("tiny", False), ("mimi_202407", False), ("tiny", True), ("mimi_202407", True)],
+                         ids=["tiny", "mimi_202407", "tiny-affine_rig", "mimi_202407-affine_rig"])
+def test_mimi_oracle_matches_transformers(name, rigged):
+    """Causal mode == the independent transformers MimiModel with mapped weights.  affine_rig: on weights whose
+    LayerNorm affine terms, layer scales and cluster usages are not degenerate (helpers.mimi_affine_rig)."""
     from csm_mlx.config import MIMI_CONFIGURATION
     from csm_mlx.weights import synthetic_mimi_weights
     from hf_mimi_map import build_hf_mimi
@@ -115,6 +117,9 @@ def test_mimi_oracle_matches_transformers(name):
     import torch
     m = dataclasses.replace(MIMI_CONFIGURATION[name], attn_mode="causal")
     w = synthetic_mimi_weights(m)
+    if rigged:
+        from helpers import mimi_affine_rig
+        w = mimi_affine_rig(m, w)
     o = OracleMimi(m, w)
     hf = build_hf_mimi(m, w)
     from golden.make_golden import pcm_fixture
