@@ -27,7 +27,7 @@ import numpy as np
 
 from . import _lib
 from .generation import (FrameCache, _check_window, _decode_batch, _resolve_sampler, _seed_list,
-                         device_processors)
+                         device_processors, processor_args)
 from .models import CSM
 from .prefix import ContextPrefix
 from .sampling import HostSampler, Sampler
@@ -66,20 +66,12 @@ class _EngineSlots:
         """Slot b's utterance samples with ``sampler`` and the ``device_processors`` pair ``processors``
         instead of the batch's (csm_slot_set_sampling); None for either: the batch's.  Right after
         ``restart(b)``."""
-        base, (bias, pen) = self.cache.sampler, self.processors or (None, None)
-        smp = base if sampler is None else sampler
-        if processors is not None:
-            bias, pen = processors
-        idx = np.asarray(bias.indices if bias else (), np.int64)
-        val = np.ascontiguousarray(bias.values if bias else (), np.float32)
-        V = self.model.n_audio_vocab
-        if idx.size and (idx.min() < 0 or idx.max() >= V):                       # no silent clamp
-            raise ValueError(f"logit_bias index outside [0, {V}): {idx.min()} .. {idx.max()}")
-        idx = np.ascontiguousarray(idx, np.int32)
+        smp = self.cache.sampler if sampler is None else sampler
+        idx, val, penalty, context = processor_args(self.processors if processors is None else processors,
+                                                    self.model.n_audio_vocab)
         s = _lib.CsmSampling(smp.temp, smp.top_k, smp.top_p, smp.min_p, smp.min_tokens_to_keep, len(idx),
                              idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                             val.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                             pen.penalty if pen else 0.0, pen.context_size if pen else 0)
+                             val.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), penalty, context)
         self._call("csm_slot_set_sampling", b, ctypes.byref(s))
 
     def prefill(self, items: Sequence[Tuple[int, np.ndarray, np.ndarray]]):

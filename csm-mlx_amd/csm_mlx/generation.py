@@ -60,6 +60,18 @@ def device_processors(logits_processors, sampler) -> Optional[Tuple[Optional[Log
     return bias, pen
 
 
+def processor_args(processors, V: int) -> Tuple[np.ndarray, np.ndarray, float, int]:
+    """A ``device_processors`` pair (None: no processors) as the engine takes it (csm_set_c0_processors,
+    csm_sampling): (bias indices int32, bias values float32, penalty, context size), the indices checked
+    against the vocabulary [0, V)."""
+    bias, pen = processors or (None, None)
+    idx = np.asarray(bias.indices if bias else (), np.int64)
+    val = np.ascontiguousarray(bias.values if bias else (), np.float32)
+    if idx.size and (idx.min() < 0 or idx.max() >= V):   # no silent clamp
+        raise ValueError(f"logit_bias index outside [0, {V}): {idx.min()} .. {idx.max()}")
+    return np.ascontiguousarray(idx, np.int32), val, (pen.penalty if pen else 0.0), (pen.context_size if pen else 0)
+
+
 def _seed_list(seed, B: int) -> np.ndarray:
     if seed is None:
         base = int.from_bytes(os.urandom(8), "little")
@@ -95,14 +107,8 @@ class FrameCache:
         if not sampler.greedy and sampler.filtered:
             self._call("csm_set_sampler_filters", sampler.top_p, sampler.min_p, sampler.min_tokens_to_keep)
         if processors is not None:
-            bias, pen = processors
-            idx = np.asarray(bias.indices if bias else (), np.int64)
-            val = np.ascontiguousarray(bias.values if bias else (), np.float32)
-            if idx.size and (idx.min() < 0 or idx.max() >= model.n_audio_vocab):   # no silent clamp
-                raise ValueError(f"logit_bias index outside [0, {model.n_audio_vocab}): {idx.min()} .. {idx.max()}")
-            idx = np.ascontiguousarray(idx, np.int32)
-            self._call("csm_set_c0_processors", len(idx), _lib.ptr(idx), _lib.ptr(val),
-                       pen.penalty if pen else 0.0, pen.context_size if pen else 0)
+            idx, val, penalty, context = processor_args(processors, model.n_audio_vocab)
+            self._call("csm_set_c0_processors", len(idx), _lib.ptr(idx), _lib.ptr(val), penalty, context)
         model._generation = self._gen = self._gen + 1
         self.frames = 0
 

@@ -165,20 +165,15 @@ struct csm_engine {
   uint8_t* done = nullptr;
   uint64_t* seeds = nullptr;
   int B = 0;
-  float temperature = 0.f;
-  int top_k = 0;
-  // mlx_lm filter chain beyond top-k (csm_set_sampler_filters; reset by csm_begin)
-  int use_top_p = 0, use_min_p = 0, min_keep = 1;
-  float top_p_cut = 0.f, log_min_p = 0.f;
-  int filters_id = 0, g_filters = -1;  // graphs capture the filter (and c0 processor) parameters by value
-  // mlx_lm make_logits_processors on the c0 logits, run inside the frame (csm_set_c0_processors; reset by
-  // csm_begin): a dense bias vector [Vpad] (zero where unset) and the repetition penalty over the last
-  // c0_context c0 codes of each utterance's history
+  // What the batch samples with (csm_kernels.h SlotSampling): the sampler of csm_begin, which also resets the
+  // rest, mlx_lm's filter chain beyond top-k (csm_set_sampler_filters) and make_logits_processors on the c0
+  // logits, run inside the frame (csm_set_c0_processors): the repetition penalty over the last batch.context
+  // c0 codes of each utterance's history and, with batch.bias 1, the dense bias vector c0_bias [Vpad] (zero
+  // where unset).  csm_engine_slots.hip checks and rounds the callers' values (sampling_*).
+  SlotSampling batch{};
   float* c0_bias = nullptr;
-  bool c0_bias_on = false;
-  float c0_penalty = 0.f;
-  int c0_context = 0;
-  bool c0_processors() const { return c0_bias_on || c0_penalty > 0.f; }
+  // the frame graphs capture the record by value: every call that writes it counts filters_id up
+  int filters_id = 0, g_filters = -1;
   int frames_run = 0;
   bool need_body = false;
   std::vector<int> prompt_len;
@@ -195,9 +190,9 @@ struct csm_engine {
   std::vector<int> slot_first;
   // Per-utterance sampling (csm_slot_set_sampling): slot_sampling[b] is what slot b's utterance samples with
   // and slot_bias[b] its dense logit bias.  The kernels read them (per_slot: their table pointers are set)
-  // from the first override after csm_begin on; until then the scalars above serve the whole batch and the
-  // frame runs exactly as without this.  A slot with no override holds the batch's values (batch_sampling);
-  // samp_own[b] marks one that has its own, samp_host mirrors the device rows for the plan (frame_plan).
+  // from the first override after csm_begin on; until then `batch` serves every row and the frame runs
+  // exactly as without this.  A slot with no override holds a copy of `batch`; samp_own[b] marks one that has
+  // its own, samp_host mirrors the device rows for the plan (frame_plan).
   SlotSampling* slot_sampling = nullptr;  // [B_max]
   float* slot_bias = nullptr;             // [B_max][Vpad]
   bool per_slot = false;
@@ -224,8 +219,6 @@ struct csm_engine {
   // graphs
   hipGraphExec_t g_body = nullptr, g_head = nullptr;
   int g_B = -1;
-  float g_temp = -1.f;
-  int g_topk = -1;
   int g_plan = -1;  // FramePlan::key() the graphs were captured for
   std::vector<void*> allocs;
   std::vector<void*> batch_allocs;
@@ -349,16 +342,26 @@ enum class HeadPhase {
 // restates the batch's sampler and processors; with it, it is the union of what the slots holding an
 // utterance need -- any non-greedy slot: a sampled plan; any with top-p / min-p: the filtered kernel for all
 // rows; any with a bias or penalty: the processors pass.  The per-slot values themselves are read from the
-// table at run time, so only a change of key() captures the frame graph again.
+// table at run time, so only a change of key() captures the frame graph again.  frame_plan is the one place
+// that decides sampled / filtered / processors: the head enqueue, dec_frame_eligible and launch_sample's
+// caller read its result.
 struct FramePlan {
   bool sampled, filtered, processors, per_slot;
   int key() const { return (sampled ? 1 : 0) | (filtered ? 2 : 0) | (processors ? 4 : 0) | (per_slot ? 8 : 0); }
 };
 FramePlan frame_plan(const csm_engine* e);
-// the batch's sampler and processors (csm_begin / csm_set_*) as a table row
-SlotSampling batch_sampling(const csm_engine* e);
-// csm_engine_slots.hip: per-slot operation, after the batch's values changed -- the rows of the slots without
-// an override follow (no-op otherwise)
+// csm_engine_slots.hip: the value checks of a row's sampler, filter chain and c0 processors and their rounding
+// into the record -- the one copy behind csm_begin, csm_set_sampler_filters, csm_set_c0_processors and
+// csm_slot_set_sampling (each keeps its own state checks); nothing is written when a check throws
+void sampling_set_sampler(SlotSampling& r, float temperature, int top_k);
+void sampling_set_filters(SlotSampling& r, double top_p, double min_p, int min_tokens_to_keep);
+// bias_mode: what r.bias becomes with n_bias > 0 (1: the batch's vector, 2: a slot's own row)
+void sampling_set_processors(const csm_engine* e, SlotSampling& r, int bias_mode, int n_bias, const int32_t* bias_idx,
+                             const float* bias_val, float repetition_penalty, int repetition_context_size);
+// the dense bias vector [Vpad] at dst, zero where unset (a repeated index: the last value); n_bias 0: untouched
+void upload_dense_bias(csm_engine* e, float* dst, int n_bias, const int32_t* bias_idx, const float* bias_val);
+// per-slot operation, after the batch's values changed -- the rows of the slots without an override follow
+// (no-op otherwise)
 void refresh_slot_sampling(csm_engine* e);
 
 // csm_engine_weights.hip

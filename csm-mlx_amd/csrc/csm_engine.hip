@@ -246,7 +246,7 @@ bool dec_frame_eligible(csm_engine* e) {
   Handoff& h = e->h_df;
   if (e->slot_mode) return false;  // its sampler counter and c0 window read the global frame index
   if (!h.on || e->B != 1 || (e->wdt != WDT_BF16 && e->wdt != WDT_Q4) || e->head_wdt != WDT_BF16) return false;
-  if (e->temperature > 0.f && (e->use_top_p || e->use_min_p)) return false;  // filters: sample_filtered_kernel
+  if (frame_plan(e).filtered) return false;  // filters: sample_filtered_kernel
   if (!csm1b_decoder(e->dec.d) || e->dec.d.n_layers != DEC_FRAME_LAYERS || e->bb.d.hidden != 2048 || e->V <= 2048 ||
       e->V > 2051 || e->K > 32 || e->dec.S_cap != e->K)
     return false;
@@ -262,8 +262,9 @@ void enqueue_dec_frame_only(csm_engine* e, hipStream_t st) {
   a.proj_tab = e->proj_tab; a.qkv0_tab = e->qkv0_tab; a.h_last = e->h_last;
   a.V = e->V; a.VP = e->Vpad; a.K = e->K; a.codes = e->codes; a.c0_logits = e->c0_logits; a.ci_logits = e->ci_logits;
   // (wnt / hnt stay zero: no kernel reads them any more)
-  a.temperature = e->temperature; a.top_k = e->top_k; a.seeds = e->seeds; a.frame_ctr = e->frame_ctr;
-  a.c0_bias = e->c0_bias_on ? e->c0_bias : nullptr; a.hist = e->hist; a.c0_penalty = e->c0_penalty; a.c0_context = e->c0_context;
+  const SlotSampling& s = e->batch;
+  a.temperature = s.temperature; a.top_k = s.top_k; a.seeds = e->seeds; a.frame_ctr = e->frame_ctr;
+  a.c0_bias = s.bias ? e->c0_bias : nullptr; a.hist = e->hist; a.c0_penalty = s.penalty; a.c0_context = s.context;
   launch_dec_frame(a, st, e->wdt == WDT_Q4);
 }
 
@@ -320,7 +321,7 @@ void launch_xsd(csm_engine* e, int M, int i, const unsigned long long* part_prev
     a.head_w = (const uint8_t*)head_tiled; a.head_nt32 = (Vp + 31) / 32; a.head_tiles = (Vp + 63) / 64; a.Vp = Vp; a.n_valid = e->V;
     a.head_out = e->ci_logits + (size_t)(i - 1) * e->B * Vp; a.head_part = part_out;
     if (sample) {
-      a.sample = 1; a.s_top_k = e->top_k; a.s_K = e->K; a.s_cb = i; a.s_temperature = e->temperature;
+      a.sample = 1; a.s_top_k = e->batch.top_k; a.s_K = e->K; a.s_cb = i; a.s_temperature = e->batch.temperature;
       a.s_seeds = e->seeds; a.s_slot_frame = e->slot_frame;
       a.s_slots = e->per_slot ? e->slot_sampling : nullptr;
     }
@@ -405,15 +406,6 @@ StepPlan plan_step(csm_engine* e, int i, bool fuse_sample) {
 
 }  // namespace
 
-SlotSampling batch_sampling(const csm_engine* e) {
-  SlotSampling s{};
-  s.temperature = e->temperature; s.top_k = e->top_k;
-  s.use_top_p = e->use_top_p; s.use_min_p = e->use_min_p; s.min_keep = e->min_keep;
-  s.top_p_cut = e->top_p_cut; s.log_min_p = e->log_min_p;
-  s.penalty = e->c0_penalty; s.context = e->c0_context; s.bias = e->c0_bias_on ? 1 : 0;
-  return s;
-}
-
 FramePlan frame_plan(const csm_engine* e) {
   FramePlan f{};
   f.per_slot = e->per_slot;
@@ -423,11 +415,11 @@ FramePlan frame_plan(const csm_engine* e) {
     f.processors |= s.bias != 0 || s.penalty > 0.f;
   };
   if (!e->per_slot) {
-    need(batch_sampling(e));
+    need(e->batch);
     return f;
   }
   for (int b = 0; b < e->B; ++b)
-    if (!e->parked_host[b]) need(e->samp_own[b] ? e->samp_host[b] : batch_sampling(e));
+    if (!e->parked_host[b]) need(e->samp_own[b] ? e->samp_host[b] : e->batch);
   return f;
 }
 
@@ -446,17 +438,18 @@ void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piec
   const bool c0_proc = phase == HeadPhase::Frame && fp.processors;
   const bool c0_sampled = !greedy || phase == HeadPhase::FromHostC0 || c0_proc;  // c0 published by sample_kernel as a single partial
   // sampled frames (top-k only): the persistent step's launch can run the sampler too
-  const bool fuse_sample = !greedy && (phase == HeadPhase::Frame || phase == HeadPhase::FromHostC0) &&
-                           (fp.per_slot ? !fp.filtered : !e->use_top_p && !e->use_min_p);
+  const bool fuse_sample = !greedy && (phase == HeadPhase::Frame || phase == HeadPhase::FromHostC0) && !fp.filtered;
   const int n0 = head_blocks(Vp, D, B, e->wdt);        // c0-head blocks (partials per row)
   const int ni = head_blocks(Vp, Dd, B, e->head_wdt);  // ci-head blocks
   auto part = [&](int cb) { return e->part + (size_t)cb * e->B_max * e->part_stride; };
   SampleParams sp{};
-  sp.ls = Vp; sp.V = V; sp.temperature = e->temperature; sp.top_k = e->top_k; sp.seeds = e->seeds;
-  sp.slot_frame = e->slot_frame; sp.K = K; sp.codes = e->codes; sp.part_stride = e->part_stride;
-  sp.use_top_p = e->use_top_p; sp.use_min_p = e->use_min_p; sp.min_keep = e->min_keep;
-  sp.top_p_cut = e->top_p_cut; sp.log_min_p = e->log_min_p;
-  sp.slots = slots; sp.slots_filtered = fp.filtered ? 1 : 0;
+  sp.ls = Vp; sp.V = V; sp.seeds = e->seeds; sp.slot_frame = e->slot_frame; sp.K = K; sp.codes = e->codes;
+  sp.part_stride = e->part_stride; sp.slots = slots;
+  {  // (the batch's values as scalars: csm_kernels.h SampleParams)
+    const SlotSampling& s = e->batch;
+    sp.temperature = s.temperature; sp.top_k = s.top_k; sp.use_top_p = s.use_top_p; sp.use_min_p = s.use_min_p;
+    sp.min_keep = s.min_keep; sp.top_p_cut = s.top_p_cut; sp.log_min_p = s.log_min_p;
+  }
   sp.forced = host_codes ? e->force : nullptr;
   // c0 = codebook0_head(h_last) (generation.py:42); greedy arg-max fused into the GEMV epilogue
   GemvParams g = gp(e);
@@ -467,17 +460,16 @@ void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piec
   if (phase == HeadPhase::C0Logits) return;
   if (c0_proc) {
     C0ProcessParams cp{};
-    cp.logits = e->c0_logits; cp.ls = Vp; cp.V = V; cp.bias = e->c0_bias_on ? e->c0_bias : nullptr; cp.penalty = e->c0_penalty;
-    cp.context = e->c0_context; cp.hist = e->hist; cp.B = B; cp.K = K; cp.F_cap = e->F_cap;
+    cp.logits = e->c0_logits; cp.ls = Vp; cp.V = V; cp.hist = e->hist; cp.B = B; cp.K = K; cp.F_cap = e->F_cap;
     cp.frame_ctr = e->frame_ctr; cp.slot_frame = e->slot_frame;
-    cp.slots = slots; cp.slot_bias = e->slot_bias;
+    cp.batch = e->batch; cp.slots = slots; cp.bias = e->c0_bias; cp.slot_bias = e->slot_bias;
     launch_c0_process(cp, st);
   }
   const bool pieces = phase == HeadPhase::HostPiece;
   const int cb_first = pieces ? piece - 1 : 0;  // the code fed forward before the first step below
   if (c0_sampled) {
     sp.logits = e->c0_logits; sp.cb = cb_first; sp.part = part(cb_first);
-    launch_sample(sp, e->wdt, B, st);
+    launch_sample(sp, B, fp.filtered, st);
   }
   const int i_lo = pieces ? piece : 1, i_hi = pieces ? std::min(piece + 1, K) : K;
   for (int i = i_lo; i < i_hi; ++i) {
@@ -545,7 +537,7 @@ void enqueue_head_phase(csm_engine* e, hipStream_t st, HeadPhase phase, int piec
     }
     if (!greedy && !pieces && !plan.sample_in_step) {
       sp.logits = e->ci_logits + (size_t)(i - 1) * B * Vp; sp.cb = i; sp.part = part(i);
-      launch_sample(sp, e->wdt, B, st);
+      launch_sample(sp, B, fp.filtered, st);
     }
   }
   if (pieces && piece < K) return;  // the frame continues with the host's next code

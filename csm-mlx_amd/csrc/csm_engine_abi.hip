@@ -56,7 +56,9 @@ int csm_begin(csm_engine* e, int B, const uint64_t* seeds, float temperature, in
       e->ahead_pending = false;
     }
     if (B <= 0) throw CsmError(CSM_ERR_ARG, "batch size out of range");
-    if (temperature < 0.f) throw CsmError(CSM_ERR_ARG, "temperature must be >= 0");
+    SlotSampling batch{};  // the sampler given here, no filter chain, no c0 processors
+    batch.min_keep = 1;
+    sampling_set_sampler(batch, temperature, top_k);
     HIPCHK(hipSetDevice(e->dev));
     ensure_batch(e, B);
     if (e->tiled_dirty) build_tiled(e);
@@ -64,14 +66,7 @@ int csm_begin(csm_engine* e, int B, const uint64_t* seeds, float temperature, in
     e->batch_epoch = e->weights_epoch;
     e->pos_host.assign(B, -1);
     e->B = B;
-    e->temperature = temperature;
-    e->top_k = top_k;
-    e->use_top_p = e->use_min_p = 0;
-    e->min_keep = 1;
-    e->top_p_cut = e->log_min_p = 0.f;
-    e->c0_bias_on = false;
-    e->c0_penalty = 0.f;
-    e->c0_context = 0;
+    e->batch = batch;
     ++e->filters_id;
     e->frames_run = 0;
     e->need_body = false;
@@ -100,15 +95,7 @@ int csm_set_sampler_filters(csm_engine* e, double top_p, double min_p, int min_t
   CSM_TRY {
     if (!e) throw CsmError(CSM_ERR_ARG, "null engine");
     if (e->frames_run > 0 || e->c0_pending) throw CsmError(CSM_ERR_STATE, "set the sampler filters before the first frame");
-    if (!(top_p >= 0.0 && top_p <= 1.0) || !(min_p >= 0.0 && min_p <= 1.0) || min_tokens_to_keep < 1)
-      throw CsmError(CSM_ERR_ARG, "top_p and min_p must lie in [0, 1], min_tokens_to_keep >= 1");
-    // mlx_lm make_sampler: top_p active in (0, 1), min_p when != 0; the cuts are the float32 values
-    // its comparisons use: 1 - top_p and log(min_p) evaluated in double, then rounded
-    e->use_top_p = top_p > 0.0 && top_p < 1.0;
-    e->use_min_p = min_p != 0.0;
-    e->top_p_cut = (float)(1.0 - top_p);
-    e->log_min_p = e->use_min_p ? (float)std::log(min_p) : 0.f;
-    e->min_keep = min_tokens_to_keep;
+    sampling_set_filters(e->batch, top_p, min_p, min_tokens_to_keep);
     ++e->filters_id;
     refresh_slot_sampling(e);
   }
@@ -120,24 +107,12 @@ int csm_set_c0_processors(csm_engine* e, int n_bias, const int32_t* bias_idx, co
   CSM_TRY {
     if (!e) throw CsmError(CSM_ERR_ARG, "null engine");
     if (e->frames_run > 0 || e->c0_pending) throw CsmError(CSM_ERR_STATE, "set the c0 processors before the first frame");
-    if (n_bias < 0 || (n_bias > 0 && (!bias_idx || !bias_val))) throw CsmError(CSM_ERR_ARG, "bad logit_bias arguments");
-    for (int i = 0; i < n_bias; ++i)
-      if (bias_idx[i] < 0 || bias_idx[i] >= e->V)
-        throw CsmError(CSM_ERR_ARG, "logit_bias index " + std::to_string(bias_idx[i]) + " outside [0, " + std::to_string(e->V) + ")");
-    if (!(repetition_penalty >= 0.f)) throw CsmError(CSM_ERR_ARG, "repetition_penalty must be >= 0");
-    if (repetition_context_size < 0 || repetition_context_size > C0_WINDOW_MAX)
-      throw CsmError(CSM_ERR_ARG, "repetition_context_size must lie in [0, " + std::to_string(C0_WINDOW_MAX) + "]");
+    SlotSampling batch = e->batch;
+    sampling_set_processors(e, batch, 1, n_bias, bias_idx, bias_val, repetition_penalty, repetition_context_size);
     HIPCHK(hipSetDevice(e->dev));
-    if (n_bias > 0) {
-      if (!e->c0_bias) e->c0_bias = (float*)e->alloc((size_t)e->Vpad * 4);
-      std::vector<float> dense(e->Vpad, 0.f);
-      for (int i = 0; i < n_bias; ++i) dense[bias_idx[i]] = bias_val[i];  // (a repeated index: the last value)
-      HIPCHK(hipMemcpyAsync(e->c0_bias, dense.data(), dense.size() * 4, hipMemcpyHostToDevice, e->st));
-      HIPCHK(hipStreamSynchronize(e->st));
-    }
-    e->c0_bias_on = n_bias > 0;
-    e->c0_penalty = repetition_penalty;
-    e->c0_context = repetition_penalty > 0.f ? repetition_context_size : 0;
+    if (n_bias > 0 && !e->c0_bias) e->c0_bias = (float*)e->alloc((size_t)e->Vpad * 4);
+    upload_dense_bias(e, e->c0_bias, n_bias, bias_idx, bias_val);
+    e->batch = batch;
     ++e->filters_id;  // the frame graphs hold these by value: re-capture
     refresh_slot_sampling(e);
   }
@@ -285,19 +260,17 @@ int csm_run_frames(csm_engine* e, int nframes, int* all_done) {
       HIPCHK(hipGetLastError());
       nframes = 0;
     }
-    // (per-slot sampling: the slots' values are read from device memory, so a join captures nothing; a
-    // change of the plan class does)
+    // The graphs hold the batch's record by value: every call that writes it (csm_begin, csm_set_*) counts
+    // filters_id up.  (Per-slot sampling: the slots' values are read from device memory, so a join captures
+    // nothing; a change of the plan class does.)
     const int plan = frame_plan(e).key();
-    if (use_graph && (e->g_B != e->B || e->g_temp != e->temperature || e->g_topk != e->top_k ||
-                      e->g_filters != e->filters_id || e->g_plan != plan || !e->g_head)) {
+    if (use_graph && (e->g_B != e->B || e->g_filters != e->filters_id || e->g_plan != plan || !e->g_head)) {
       if (e->frames_run > 0) HIPCHK(hipStreamSynchronize(e->st));  // frames enqueued without a wait still replay the old graphs
       if (e->g_body) (void)hipGraphExecDestroy(e->g_body);
       if (e->g_head) (void)hipGraphExecDestroy(e->g_head);
       e->g_body = capture(e, enqueue_body);
       e->g_head = capture(e, enqueue_head);
       e->g_B = e->B;
-      e->g_temp = e->temperature;
-      e->g_topk = e->top_k;
       e->g_filters = e->filters_id;
       e->g_plan = plan;
     }

@@ -266,7 +266,7 @@ int csm_bench_dec_xsd(csm_engine* e, int iters, float* avg_us, double* bytes) {
     // The replay recomputes the last frame's last codebook step (i = K - 1) from the same partials of
     // step K - 2: the same K/V rows, codes, logits and partials are written again.
     const int Vp = e->Vpad, i = K - 1;
-    const bool greedy = e->temperature <= 0.f;
+    const bool greedy = !frame_plan(e).sampled;
     auto part = [&](int cb) { return e->part + (size_t)cb * e->B_max * e->part_stride; };
     const int pn = greedy ? head_blocks(Vp, e->Dd, M, e->head_wdt) : 1;
     const size_t D = e->Dd, F = e->dec.d.intermediate, QKV = e->dec.qkv_rows(), HKV = e->dec.d.n_kv_heads, HD = e->dec.d.head_dim;

@@ -11,6 +11,9 @@
 // row b of a device table the sample kernels, the persistent step's sampler and c0_process_kernel read at run
 // time, written on the engine stream like the rest of a slot's state, so frames already enqueued never see a
 // later write and a join captures nothing; csm_engine.hip frame_plan picks the frame's plan class from the rows.
+// The batch's values are the same record (csm_engine::batch); the value checks and the rounding into a record
+// that csm_begin, csm_set_sampler_filters, csm_set_c0_processors and csm_slot_set_sampling share are here
+// (sampling_set_*, upload_dense_bias).
 #include "csm_engine.h"
 
 namespace {
@@ -75,7 +78,7 @@ void slot_reset(csm_engine* e, int b, uint64_t seed, bool park) {
   p.done = e->done; p.n_frames = e->n_frames; p.slot_frame = e->slot_frame; p.codes = e->codes; p.parked = e->parked;
   p.pos = e->pos; p.seeds = e->seeds; p.h_last = e->h_last; p.b = b; p.K = e->K; p.D = e->D; p.seed = seed; p.park = park ? 1 : 0;
   // the slot forgets its utterance's own sampling: the next one starts from the batch's
-  p.sampling = e->per_slot ? e->slot_sampling : nullptr; p.batch = batch_sampling(e);
+  p.sampling = e->per_slot ? e->slot_sampling : nullptr; p.batch = e->batch;
   e->samp_own[b] = 0;
   hipLaunchKernelGGL(slot_reset_kernel, dim3(1), dim3(256), 0, e->st, p);
   HIPCHK(hipGetLastError());
@@ -101,38 +104,66 @@ __global__ void slot_sampling_set_kernel(SlotSampling* table, int b, SlotSamplin
 // The whole table from the host's view of it: the rows of the slots with an override, the batch's for the rest
 void upload_slot_sampling(csm_engine* e) {
   std::vector<SlotSampling> rows(e->B);
-  for (int b = 0; b < e->B; ++b) rows[b] = e->samp_own[b] ? e->samp_host[b] : batch_sampling(e);
+  for (int b = 0; b < e->B; ++b) rows[b] = e->samp_own[b] ? e->samp_host[b] : e->batch;
   HIPCHK(hipMemcpyAsync(e->slot_sampling, rows.data(), rows.size() * sizeof(SlotSampling), hipMemcpyHostToDevice, e->st));
   HIPCHK(hipStreamSynchronize(e->st));  // (the host rows are released on return)
 }
 
-// csm_sampling -> a table row, with the value checks of csm_set_sampler_filters and csm_set_c0_processors
+// csm_sampling -> a table row.  A greedy utterance has no filter chain, whatever top_p and min_p say (the
+// batch's csm_set_sampler_filters keeps them: frame_plan ignores the filters of a greedy record).
 SlotSampling checked_row(csm_engine* e, const csm_sampling& s) {
-  if (!(s.temperature >= 0.f)) throw CsmError(CSM_ERR_ARG, "temperature must be >= 0");
-  if (!(s.top_p >= 0.0 && s.top_p <= 1.0) || !(s.min_p >= 0.0 && s.min_p <= 1.0) || s.min_tokens_to_keep < 1)
-    throw CsmError(CSM_ERR_ARG, "top_p and min_p must lie in [0, 1], min_tokens_to_keep >= 1");
-  if (s.n_bias < 0 || (s.n_bias > 0 && (!s.bias_idx || !s.bias_val))) throw CsmError(CSM_ERR_ARG, "bad logit_bias arguments");
-  for (int i = 0; i < s.n_bias; ++i)
-    if (s.bias_idx[i] < 0 || s.bias_idx[i] >= e->V)
-      throw CsmError(CSM_ERR_ARG, "logit_bias index " + std::to_string(s.bias_idx[i]) + " outside [0, " + std::to_string(e->V) + ")");
-  if (!(s.repetition_penalty >= 0.f)) throw CsmError(CSM_ERR_ARG, "repetition_penalty must be >= 0");
-  if (s.repetition_context_size < 0 || s.repetition_context_size > C0_WINDOW_MAX)
-    throw CsmError(CSM_ERR_ARG, "repetition_context_size must lie in [0, " + std::to_string(C0_WINDOW_MAX) + "]");
   SlotSampling r{};
-  r.temperature = s.temperature; r.top_k = s.top_k;
-  // (the cuts as csm_set_sampler_filters rounds them; a greedy utterance has no filter chain)
-  r.use_top_p = s.temperature > 0.f && s.top_p > 0.0 && s.top_p < 1.0;
-  r.use_min_p = s.temperature > 0.f && s.min_p != 0.0;
-  r.top_p_cut = (float)(1.0 - s.top_p);
-  r.log_min_p = r.use_min_p ? (float)std::log(s.min_p) : 0.f;
-  r.min_keep = s.min_tokens_to_keep;
-  r.penalty = s.repetition_penalty;
-  r.context = s.repetition_penalty > 0.f ? s.repetition_context_size : 0;
-  r.bias = s.n_bias > 0 ? 2 : 0;
+  sampling_set_sampler(r, s.temperature, s.top_k);
+  sampling_set_filters(r, s.top_p, s.min_p, s.min_tokens_to_keep);
+  sampling_set_processors(e, r, 2, s.n_bias, s.bias_idx, s.bias_val, s.repetition_penalty, s.repetition_context_size);
+  if (!(r.temperature > 0.f)) {
+    r.use_top_p = r.use_min_p = 0;
+    r.log_min_p = 0.f;
+  }
   return r;
 }
 
 }  // namespace
+
+void sampling_set_sampler(SlotSampling& r, float temperature, int top_k) {
+  if (!(temperature >= 0.f)) throw CsmError(CSM_ERR_ARG, "temperature must be >= 0");  // (refuses NaN too)
+  r.temperature = temperature;
+  r.top_k = top_k;
+}
+
+void sampling_set_filters(SlotSampling& r, double top_p, double min_p, int min_tokens_to_keep) {
+  if (!(top_p >= 0.0 && top_p <= 1.0) || !(min_p >= 0.0 && min_p <= 1.0) || min_tokens_to_keep < 1)
+    throw CsmError(CSM_ERR_ARG, "top_p and min_p must lie in [0, 1], min_tokens_to_keep >= 1");
+  // mlx_lm make_sampler: top_p active in (0, 1), min_p when != 0; the cuts are the float32 values
+  // its comparisons use: 1 - top_p and log(min_p) evaluated in double, then rounded
+  r.use_top_p = top_p > 0.0 && top_p < 1.0;
+  r.use_min_p = min_p != 0.0;
+  r.top_p_cut = (float)(1.0 - top_p);
+  r.log_min_p = r.use_min_p ? (float)std::log(min_p) : 0.f;
+  r.min_keep = min_tokens_to_keep;
+}
+
+void sampling_set_processors(const csm_engine* e, SlotSampling& r, int bias_mode, int n_bias, const int32_t* bias_idx,
+                             const float* bias_val, float repetition_penalty, int repetition_context_size) {
+  if (n_bias < 0 || (n_bias > 0 && (!bias_idx || !bias_val))) throw CsmError(CSM_ERR_ARG, "bad logit_bias arguments");
+  for (int i = 0; i < n_bias; ++i)
+    if (bias_idx[i] < 0 || bias_idx[i] >= e->V)
+      throw CsmError(CSM_ERR_ARG, "logit_bias index " + std::to_string(bias_idx[i]) + " outside [0, " + std::to_string(e->V) + ")");
+  if (!(repetition_penalty >= 0.f)) throw CsmError(CSM_ERR_ARG, "repetition_penalty must be >= 0");
+  if (repetition_context_size < 0 || repetition_context_size > C0_WINDOW_MAX)
+    throw CsmError(CSM_ERR_ARG, "repetition_context_size must lie in [0, " + std::to_string(C0_WINDOW_MAX) + "]");
+  r.penalty = repetition_penalty;
+  r.context = repetition_penalty > 0.f ? repetition_context_size : 0;
+  r.bias = n_bias > 0 ? bias_mode : 0;
+}
+
+void upload_dense_bias(csm_engine* e, float* dst, int n_bias, const int32_t* bias_idx, const float* bias_val) {
+  if (n_bias <= 0) return;
+  std::vector<float> dense(e->Vpad, 0.f);
+  for (int i = 0; i < n_bias; ++i) dense[bias_idx[i]] = bias_val[i];
+  HIPCHK(hipMemcpyAsync(dst, dense.data(), dense.size() * 4, hipMemcpyHostToDevice, e->st));
+  HIPCHK(hipStreamSynchronize(e->st));  // (the host vector is released on return)
+}
 
 void refresh_slot_sampling(csm_engine* e) {
   if (!e->per_slot) return;
@@ -162,14 +193,9 @@ int csm_slot_set_sampling(csm_engine* e, int b, const csm_sampling* s) {
     if (e->parked_host[b]) throw CsmError(CSM_ERR_STATE, "slot " + std::to_string(b) + " holds no utterance: csm_slot_restart first");
     if (e->frames_run > e->slot_first[b])
       throw CsmError(CSM_ERR_STATE, "slot " + std::to_string(b) + ": its utterance has already run a frame");
-    const SlotSampling row = s ? checked_row(e, *s) : batch_sampling(e);
+    const SlotSampling row = s ? checked_row(e, *s) : e->batch;
     HIPCHK(hipSetDevice(e->dev));
-    if (s && s->n_bias > 0) {  // the slot's dense bias row, zero where unset (a repeated index: the last value)
-      std::vector<float> dense(e->Vpad, 0.f);
-      for (int i = 0; i < s->n_bias; ++i) dense[s->bias_idx[i]] = s->bias_val[i];
-      HIPCHK(hipMemcpyAsync(e->slot_bias + (size_t)b * e->Vpad, dense.data(), dense.size() * 4, hipMemcpyHostToDevice, e->st));
-      HIPCHK(hipStreamSynchronize(e->st));
-    }
+    if (s) upload_dense_bias(e, e->slot_bias + (size_t)b * e->Vpad, s->n_bias, s->bias_idx, s->bias_val);  // the slot's own row
     e->samp_own[b] = s ? 1 : 0;
     e->samp_host[b] = row;
     if (s && !e->per_slot) {  // the first override of this batch: every slot's row, the batch's for the others

@@ -250,13 +250,17 @@ struct AttnParams {
   int blk;  // ATTN_FRAMES: rows per frame (the codec's downsample_stride)
 };
 
-// One row of the per-slot sampling table (csm_slot_set_sampling, csm_engine_slots.hip): what slot b's
-// utterance samples with when the batch runs per-slot -- the fields SampleParams and C0ProcessParams carry
-// as scalars for the whole batch.  Every kernel that reads it handles one row per workgroup, so a row's
-// values are block-uniform.
+// How one row samples: the sampler (temperature, top_k), mlx_lm's filter chain beyond top-k and the c0 logits
+// processors -- the one record of these values from the host to the kernels.  The engine holds the batch's
+// (csm_engine::batch: csm_begin / csm_set_*) and, in per-slot operation, a device table with a row per slot
+// (csm_slot_set_sampling, csm_engine_slots.hip) that overrides it; csm_engine_slots.hip checks and rounds the
+// caller's values into it.  Every kernel that reads it handles one row per workgroup, so a row's values are
+// block-uniform; c0_process_kernel takes the batch's record by value too (sampler.h row_sampling).
 struct SlotSampling {
   float temperature;  // 0: greedy -- the first max of the raw logits, no noise, 1 / temperature never taken
   int top_k;
+  // top_p keeps entries whose ascending cumulative probability > top_p_cut = float32(1 - top_p); min_p keeps
+  // lp >= best + log_min_p (float32(log(min_p))) and the first min_keep ranks (sample_filtered_kernel)
   int use_top_p, use_min_p, min_keep;
   float top_p_cut, log_min_p;
   float penalty;      // 0: no repetition penalty
@@ -264,6 +268,10 @@ struct SlotSampling {
   int bias;           // 0: none, 1: the batch's dense bias (C0ProcessParams::bias), 2: the slot's own row
 };
 
+// The sample kernels' launch block carries the batch's sampler and filter chain as scalars, not as the record:
+// with a SlotSampling by value sample_filtered_kernel's kernarg read becomes one 8-dword load and the kernel
+// spills 10 SGPRs instead of 4 (profiles/sampling_record_kres.txt).  The head enqueue fills them from the
+// engine's record (csm_engine.hip enqueue_head_phase).
 struct SampleParams {
   const float* logits;  // [B][ls]
   int ls, V;            // V = number of valid logits
@@ -276,16 +284,10 @@ struct SampleParams {
   unsigned long long* part;  // optional: publish the code as partial [b * part_stride]
   int part_stride;
   const int* forced;    // optional [B][K]: teacher forcing -- the code is forced[b][cb], logits untouched
-  // mlx_lm filter chain beyond top-k (sample_filtered_kernel): top_p keeps entries whose ascending
-  // cumulative probability > top_p_cut = float32(1 - top_p); min_p keeps lp >= best + log_min_p
-  // (float32(log(min_p))) and the first min_keep ranks
-  int use_top_p, use_min_p, min_keep;
+  int use_top_p, use_min_p, min_keep;  // (SlotSampling's fields of these names)
   float top_p_cut, log_min_p;
-  // per-slot operation: row b's temperature, top_k and filters come from slots[b] instead of the scalars above
-  // (null: the scalars).  slots_filtered: some slot holding an utterance has a filter on, so every row runs
-  // sample_filtered_kernel (what the scalars decide otherwise)
+  // row b samples with slots[b] in per-slot operation, with the batch's values above otherwise (slots null)
   const SlotSampling* slots;
-  int slots_filtered;
 };
 
 // mlx_lm make_logits_processors on the c0 logits, run inside the frame (csm_set_c0_processors; c0_process.h
@@ -296,17 +298,16 @@ constexpr int C0_WINDOW_MAX = 256;
 struct C0ProcessParams {
   float* logits;       // [B][ls], transformed in place
   int ls, V;
-  const float* bias;   // [ls] dense, zero where unset; null: no bias
-  float penalty;       // 0: no repetition penalty
-  int context;
   const int* hist;     // [F_cap][B][K]
   int B, K, F_cap;
   const int* frame_ctr;   // the global frame index (where the history is written)
   const int* slot_frame;  // [B] each utterance's own frame index (how much of the history is its own)
-  // per-slot operation: row b's penalty, context and bias (SlotSampling::bias; its own row: slot_bias[b])
-  // come from slots[b] (null: the scalars above)
+  // row b's penalty, context and bias mode come from slots[b] in per-slot operation, from the batch's record
+  // otherwise (slots null); the mode picks the bias vector
+  SlotSampling batch;
   const SlotSampling* slots;
-  const float* slot_bias;  // [B_max][ls]
+  const float* bias;       // [ls] the batch's dense bias, zero where unset (mode 1)
+  const float* slot_bias;  // [B_max][ls] the slots' own rows (mode 2)
 };
 void launch_c0_process(const C0ProcessParams& p, hipStream_t st);
 
@@ -344,7 +345,8 @@ void launch_rmsnorm_rows(const float* x, int xs, const float* w, float eps, int 
 // R = wdc_chunk(D) consecutive intermediate columns per chunk (0: no chunk-major copy for this width)
 int wdc_chunk(int D);
 bool gemv_nt(int tag);                       // non-temporal weight loads for this stack tag
-void launch_sample(const SampleParams& p, int wdt, int B, hipStream_t st);
+// filtered (FramePlan::filtered): the rows run the filter chain's kernel -- never a forced launch (p.forced)
+void launch_sample(const SampleParams& p, int B, bool filtered, hipStream_t st);
 void launch_advance(const AdvanceParams& p, hipStream_t st);
 // Teacher-forced cross entropy (mlx cross_entropy, trainer.py:271-312): out[b][cb] =
 // logsumexp(logits[:V]) - logits[forced[b][cb]] for c0 rows [B][Vp] and ci rows [K-1][B][Vp].

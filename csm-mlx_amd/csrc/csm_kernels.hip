@@ -948,13 +948,12 @@ __global__ __launch_bounds__(256) void rmsnorm_rows_kernel(const float* x, int x
 
 // One block per utterance.  Greedy: first max (mx.argmax, generation.py:51-52).  Else Gumbel-max
 // over logits*(1/temp) restricted to values >= the top_k-th largest (radix select) -- mlx_lm
-// make_sampler(temp, top_k) semantics with the build's counter-based RNG.  The chosen code's
-// audio embedding (embed_audio, models.py:79-80) is gathered into the next decoder input row.
+// make_sampler(temp, top_k) semantics with the build's counter-based RNG.  The chosen code goes to
+// codes[b][cb] and, as a single partial, to the next step's row gather.
 // The threshold, the arg-max and the Gumbel pass are sampler.h's.
 using namespace sampler;
 constexpr int SAMPLE_CMAX = 512;  // compacted top-k survivors (more ties than this: the in-place loop)
 
-template <typename WT>
 __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
   __shared__ uint32_t hist[256];
   __shared__ uint32_t wsum[4];
@@ -1283,17 +1282,14 @@ __global__ void advance_kernel(AdvanceParams p) {
 __global__ __launch_bounds__(256) void c0_process_kernel(C0ProcessParams p) {
   __shared__ int win[C0_WINDOW_MAX];
   const int b = blockIdx.x, f = p.frame_ctr[0];
-  // per-slot operation: row b's own penalty, window and bias (block-uniform, read once); a row with none of
-  // them passes through unchanged
-  const SlotSampling* row = p.slots ? p.slots + b : nullptr;
-  const float penalty = row ? row->penalty : p.penalty;
-  const int context = row ? row->context : p.context;
-  const float* bias = !row ? p.bias : row->bias == 2 ? p.slot_bias + (size_t)b * p.ls : row->bias == 1 ? p.bias : nullptr;
-  const int n = c0_window_n(min(p.slot_frame[b], f), context, penalty);  // never a predecessor's codes in the same slot
+  // a row with no penalty and no bias passes through unchanged
+  const SlotSampling s = row_sampling(p.slots, b, p.batch);
+  const float* bias = s.bias == 2 ? p.slot_bias + (size_t)b * p.ls : s.bias == 1 ? p.bias : nullptr;
+  const int n = c0_window_n(min(p.slot_frame[b], f), s.context, s.penalty);  // never a predecessor's codes in the same slot
   for (int j = threadIdx.x; j < n; j += 256) win[j] = c0_window_code_ring(p.hist, f, j, b, p.B, p.K, p.F_cap);
   __syncthreads();
   float* lg = p.logits + (size_t)b * p.ls;
-  for (int v = threadIdx.x; v < p.V; v += 256) lg[v] = c0_processed(lg[v], v, bias, win, n, penalty);
+  for (int v = threadIdx.x; v < p.V; v += 256) lg[v] = c0_processed(lg[v], v, bias, win, n, s.penalty);
 }
 
 // ============================================================================ launchers
@@ -1462,17 +1458,13 @@ void launch_rmsnorm_rows(const float* x, int xs, const float* w, float eps, int 
 
 int wdc_chunk(int D) { return D == 1024 ? 16 : (D == 2048 ? 8 : 0); }
 
-void launch_sample(const SampleParams& p, int wdt, int B, hipStream_t st) {
+void launch_sample(const SampleParams& p, int B, bool filtered, hipStream_t st) {
   if (p.V > 256 * SAMPLE_NPT) {
     fprintf(stderr, "csm: sampler supports V <= %d (got %d)\n", 256 * SAMPLE_NPT, p.V);
     abort();
   }
-  if (!p.forced && (p.slots ? p.slots_filtered != 0 : p.temperature > 0.f && (p.use_top_p || p.use_min_p))) {
-    hipLaunchKernelGGL(sample_filtered_kernel, dim3(B), dim3(256), 0, st, p);
-    return;
-  }
-  if (wdt == WDT_BF16) hipLaunchKernelGGL(sample_kernel<bf16_t>, dim3(B), dim3(256), 0, st, p);
-  else hipLaunchKernelGGL(sample_kernel<float>, dim3(B), dim3(256), 0, st, p);
+  if (filtered && !p.forced) hipLaunchKernelGGL(sample_filtered_kernel, dim3(B), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(256), 0, st, p);
 }
 
 // One block per (codebook, utterance) row: max, then sum of exp(l - max) in fp32 (wave shuffles +
@@ -1507,7 +1499,7 @@ void launch_forced_ce(const float* c0, const float* ci, const int* forced, float
 }
 
 void launch_c0_process(const C0ProcessParams& p, hipStream_t st) {
-  if (p.context < 0 || p.context > C0_WINDOW_MAX) throw CsmError(CSM_ERR_ARG, "c0 processors: window beyond C0_WINDOW_MAX");
+  if (p.batch.context < 0 || p.batch.context > C0_WINDOW_MAX) throw CsmError(CSM_ERR_ARG, "c0 processors: window beyond C0_WINDOW_MAX");
   hipLaunchKernelGGL(c0_process_kernel, dim3(p.B), dim3(256), 0, st, p);
 }
 

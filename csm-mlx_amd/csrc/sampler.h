@@ -153,8 +153,13 @@ __device__ __forceinline__ void greedy_pass(int tid, int V, Logit&& logit, doubl
   gumbel_pass<NT, NPT>(tid, V, -INFINITY, 1.0f, logit, [](int, int) { return 0.0; }, best, bi);
 }
 
-// Row b's temperature / top_k in per-slot operation (slots non-null: csm_kernels.h SlotSampling), else the
-// launch's scalars.  b is the workgroup's row, so the result is block-uniform: read once, ahead of the loops.
+// Row b's record (csm_kernels.h SlotSampling): its slot's in per-slot operation (slots non-null), else the
+// batch's.  b is the workgroup's row, so the result is block-uniform: read once, ahead of the loops.
+__device__ __forceinline__ SlotSampling row_sampling(const SlotSampling* slots, int b, const SlotSampling& batch) {
+  return slots ? slots[b] : batch;
+}
+// The same for a launch block that carries the batch's temperature / top_k as scalars (SampleParams,
+// DecStepXsArgs: csm_kernels.h says why)
 __device__ __forceinline__ float row_temperature(const SlotSampling* slots, int b, float temperature) {
   return slots ? slots[b].temperature : temperature;
 }
