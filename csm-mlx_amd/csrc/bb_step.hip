@@ -241,10 +241,9 @@ __device__ __forceinline__ void phase_qkv(Ctx& c, int l, int pos, const WQ& W, b
       b *= rs;
     }
     if (n < (HQ + HKV) * HD) {
-      const float2 cs = c.L.rope[(n % HD) / 2];
-      const float y0 = a * cs.x - b * cs.y, y1 = b * cs.x + a * cs.y;
-      a = y0;
-      b = y1;
+      const float2 y = rope_rotate(a, b, c.L.rope[(n % HD) / 2]);
+      a = y.x;
+      b = y.y;
     }
     u64* g = c.buf(G_QKV, QKV);
     gput(g + n, a, c.tag());
@@ -567,10 +566,9 @@ __device__ __forceinline__ void phase_qkv4(Ctx& c, int l, int pos, const WQ4& W)
     const float rs = row_rs(c);
     float a = c.L.wsum[i0 & 7][i0 >> 3] * rs, b = c.L.wsum[(i0 + 1) & 7][(i0 + 1) >> 3] * rs;
     if (n < (HQ + HKV) * HD) {
-      const float2 cs = c.L.rope[(n % HD) / 2];
-      const float y0 = a * cs.x - b * cs.y, y1 = b * cs.x + a * cs.y;
-      a = y0;
-      b = y1;
+      const float2 y = rope_rotate(a, b, c.L.rope[(n % HD) / 2]);
+      a = y.x;
+      b = y.y;
     }
     u64* g = c.buf(G_QKV, QKV);
     gput(g + n, a, c.tag());

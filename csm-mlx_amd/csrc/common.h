@@ -115,6 +115,13 @@ __device__ __forceinline__ float gelu_tanh_f(float x) {
 __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.7071067811865476f)); }
 __device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : expm1f(x); }
 
+// RoPE on the interleaved pair (a, b) = elements (2i, 2i + 1) of a head (attention.py:157-177), cs =
+// (cos, sin) of the position from the table.  The products are left to the compiler's contraction, the
+// same at every site (not written as fmaf).  The Mimi kernels rotate another layout.
+__device__ __forceinline__ float2 rope_rotate(float a, float b, float2 cs) {
+  return make_float2(a * cs.x - b * cs.y, b * cs.x + a * cs.y);
+}
+
 // Row -> (utterance, position) map shared by the projection epilogues and attention.
 //   b(m)   = b_off + m / T
 //   pos(m) = (pos_arr ? pos_arr[b(m)] : 0) + pos_const + m % T

@@ -179,9 +179,9 @@ __device__ __forceinline__ void gemv_epilogue_pair(const GemvParams& p, int m, i
       const int d = nn % p.hd;
       if (n < qn + kn) {
         const float2 cs = *reinterpret_cast<const float2*>(p.rope + ((size_t)pos * (p.hd >> 1) + (d >> 1)) * 2);
-        const float y0 = a * cs.x - b * cs.y, y1 = b * cs.x + a * cs.y;
-        a = y0;
-        b = y1;
+        const float2 y = rope_rotate(a, b, cs);
+        a = y.x;
+        b = y.y;
       }
       float* o;
       if (p.qkv_tab) {  // table build: the whole (RoPE'd q, k | v) row of row m

@@ -13,6 +13,7 @@
 // Weights are streamed straight to VGPRs with 16-B loads (GEMV / M <= 16 regime: no LDS
 // round trip); x rows are tiny and served from L1/L2.  The GEMVs' gather prologue and the
 // parts of their tail are gemm_parts.h's, shared with the int4 GEMV and the matrix-core kernels.
+#include "attn32.h"
 #include "c0_process.h"
 #include "csm_kernels.h"
 #include "engine_util.h"
@@ -612,20 +613,17 @@ __device__ __forceinline__ void attn_block(const AttnParams& p, int m, int kvh, 
 }
 
 // Short causal attention (depth decoder: <= 32 cached positions, generation.py:70-77): one wave per
-// (row, q head); lanes (key j, half of the head dims) compute the scores.  Every K half-row and V row
-// is loaded up front with 16-B loads straight to VGPRs -- one memory round trip instead of
-// attn_block's staged chunk pipeline.  P.V (as dec_frame's DF_PV 2): lane = (key half kv = lane >> 5:
-// keys 16 kv .. 16 kv + 15, dims 4 dq .. 4 dq + 3, dq = lane & 31), so a key's V row is one 16-B load
-// per lane (16 loads per wave instead of 64 of 4 B); each half sums its keys in order and the halves
-// are added once (keys 0-15 first); lanes dq < 32 return dims 4 dq .. 4 dq + 3.  fp32 throughout:
-// scores, softmax (max-subtracted, one pass: all keys fit one wave).  With g_tab set (decoder layer 0,
-// codebook steps >= 2) the row's q and its key/value at pos come from the folded layer-0 table (see
-// AttnParams).
+// (row, q head), the arithmetic of attn32.h (scores, softmax, P.V, with its two lane maps).  Every K
+// half-row and V row is loaded up front with 16-B loads straight to VGPRs -- one memory round trip
+// instead of attn_block's staged chunk pipeline; a key's V row is one 16-B load per lane (16 loads per
+// wave instead of 64 of 4 B); lanes dq < 32 return dims 4 dq .. 4 dq + 3.  With g_tab set (decoder
+// layer 0, codebook steps >= 2) the row's q and its key/value at pos come from the folded layer-0 table
+// (see AttnParams).
 template <int HD, int NMAX>
 __device__ __forceinline__ void attn_short_head(const AttnParams& p, int m, int h, int lane, float* qsh,
                                                 float (&o)[4], bool write_kv, bool write_code, bool copy_res,
                                                 int* code_out) {
-  static_assert(HD == 128 && NMAX == 32, "key halves of 16 x 32 lanes x 4 dims");
+  static_assert(HD == attn32::HD && NMAX == attn32::NMAX, "key halves of 16 x 32 lanes x 4 dims");
   constexpr int V4 = HD / 4;
   const int G = p.Hq / p.Hkv, kvh = h / G;
   const int b = p.rm.b(m), pos = p.rm.pos(m);
@@ -688,48 +686,16 @@ __device__ __forceinline__ void attn_short_head(const AttnParams& p, int m, int 
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  // scores (fp32), softmax over the n live keys, P.V in key order
-  float s;
-  {
-    const f32x4* qr = reinterpret_cast<const f32x4*>(qsh + hh * (HD / 2));
-    float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
-#pragma unroll
-    for (int d4 = 0; d4 < H4; ++d4) {
-      const f32x4 a = kr[d4], q4 = qr[d4];
-      d0 = fmaf(q4.x, a.x, d0);
-      d1 = fmaf(q4.y, a.y, d1);
-      d2 = fmaf(q4.z, a.z, d2);
-      d3 = fmaf(q4.w, a.w, d3);
-    }
-    const float part = (d0 + d1) + (d2 + d3);
-    const float other = __shfl_xor(part, 32, 64);
-    s = hh == 0 ? part + other : other + part;  // half 0 + half 1 on both lanes of a key
-    if (kj >= n) s = -INFINITY;
-  }
-  const float new_m = wave_max(s);
-  const float pj = (kj < n) ? expf(s - new_m) : 0.f;
-  const float l_run = wave_sum(hh == 0 ? pj : 0.f);
-  const int pji = __float_as_int(pj);
+  // scores (fp32), softmax over the n live keys, P.V in key order (attn32.h)
+  const float s = attn32::score(kr, reinterpret_cast<const f32x4*>(qsh + hh * (HD / 2)), hh);
+  const attn32::Probs pr = attn32::softmax(s, kj, hh, n);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int u = 0; u < NMAX / 2; ++u) {
-    const float pa = __int_as_float(__builtin_amdgcn_readlane(pji, u));
-    const float pb = __int_as_float(__builtin_amdgcn_readlane(pji, 16 + u));
-    const float pw = kv ? pb : pa;
-    if (16 * kv + u < n) {
-      acc.x = fmaf(pw, vv[u].x, acc.x);
-      acc.y = fmaf(pw, vv[u].y, acc.y);
-      acc.z = fmaf(pw, vv[u].z, acc.z);
-      acc.w = fmaf(pw, vv[u].w, acc.w);
-    }
-  }
-  const float inv = 1.f / l_run;
-  const float t0 = __shfl_xor(acc.x, 32, 64), t1 = __shfl_xor(acc.y, 32, 64), t2 = __shfl_xor(acc.z, 32, 64),
-              t3 = __shfl_xor(acc.w, 32, 64);
-  o[0] = (acc.x + t0) * inv;  // (lanes < 32: keys 0-15 + keys 16-31)
-  o[1] = (acc.y + t1) * inv;
-  o[2] = (acc.z + t2) * inv;
-  o[3] = (acc.w + t3) * inv;
+  attn32::pv(acc, pr.pji, vv, 0, kv, n);
+  const f32x4 r = attn32::finish(acc, pr.l_run);
+  o[0] = r.x;
+  o[1] = r.y;
+  o[2] = r.z;
+  o[3] = r.w;
 }
 
 template <int HD, int NMAX>
@@ -738,14 +704,12 @@ __global__ __launch_bounds__(64) void attn_short_kernel(AttnParams p) {
   const int m = blockIdx.x / p.Hq, h = blockIdx.x % p.Hq, lane = threadIdx.x, dq = lane & 31;
   float o[4];
   attn_short_head<HD, NMAX>(p, m, h, lane, qsh, o, true, true, true, nullptr);
-  // half-group sums for an int4 o_proj: 32 columns = 8 lanes, each lane's 4 in column order, then
-  // the lanes' sums in a butterfly (lanes 32-63 mirror 0-31 and store nothing)
-  float hsum = (o[0] + o[1]) + (o[2] + o[3]);
-#pragma unroll
-  for (int x = 1; x < 8; x <<= 1) hsum += __shfl_xor(hsum, x, 64);
+  // half-group sums for an int4 o_proj (lanes 32-63 mirror 0-31 and store nothing)
+  const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
+  const float hsum = attn32::half_group_sum(ov);
   if (lane < 32) {
     float* out = p.out + (size_t)m * p.os + h * HD + 4 * dq;
-    *reinterpret_cast<float4*>(out) = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(out) = ov;
     if (p.xs_out) {  // the operand of the streaming o_proj GEMM (gemm_xs.hip)
       xs::store4(p.xs_out, p.xs_K, m, h * HD + 4 * dq, o);
       if (p.hs_out && (dq & 7) == 0) p.hs_out[(size_t)((h * HD + 4 * dq) / 32) * xs::HS_ROWS + m] = hsum;

@@ -34,6 +34,7 @@
 // max subtraction, reductions in fixed orders (deterministic run to run).
 #include <type_traits>
 
+#include "attn32.h"
 #include "c0_process.h"
 #include "csm_kernels.h"
 #include "handoff.h"
@@ -414,10 +415,9 @@ __device__ __forceinline__ void qkv_publish(Ctx& c, int pos0) {
     }
     if (n < (HQ + HKV) * HD) {
       const int d = n % HD;
-      const float2 cs = c.L.rope[m][d / 2];
-      const float y0 = a * cs.x - b * cs.y, y1 = b * cs.x + a * cs.y;
-      a = y0;
-      b = y1;
+      const float2 y = rope_rotate(a, b, c.L.rope[m][d / 2]);
+      a = y.x;
+      b = y.y;
     }
     c.put(G_QKV, MAXM * QKV, (size_t)m * QKV + n, a, rr);
     c.put(G_QKV, MAXM * QKV, (size_t)m * QKV + n + 1, b, rr);
@@ -481,90 +481,45 @@ __device__ __forceinline__ void gather_qkv(Ctx& c, const u64* buf, int pos0, con
 }
 
 // Attention of rows m < M (positions pos0 + m) over keys 0..pos0+m, all in c.L.Ks / Vs (kv_store +
-// qkv_place).  Every WG computes all heads (wave = head), as attn_short_head: lane = (key kj =
-// lane & 31, half hh of the head dims), scores from two half dots added by one shuffle,
-// max-subtracted softmax, P.V in key order with the V rows read 8 keys at a time (all in flight
-// together; rows past the last key are read but not used): one 16-B V read per key over key halves
-// (lane >> 5), the halves' sums exchanged once -- the loop is issue-bound, and 4-B or 8-B reads per
+// qkv_place).  Every WG computes all heads (wave = head) with the arithmetic and lane maps of attn32.h;
+// the V rows are read 8 keys at a time (all in flight together; rows past the last key are read but not
+// used): one 16-B V read per key over key halves -- the loop is issue-bound, and 4-B or 8-B reads per
 // key cost 56 us per frame more (profiles/r03_ab_pairs.txt).  The new K/V rows go to the cache,
 // spread over the workgroups, for later steps.
 template <int M, bool Q4 = false>
 __device__ __forceinline__ void phase_attn(Ctx& c, int pos0, int layer) {
+  static_assert(HD == attn32::HD, "attn32.h: head_dim 128");
   const int h = c.wave, g = h / (HQ / HKV);
-  const float scale = 0.08838834764831845f;  // 1 / sqrt(128)
   const int kj = c.lane & 31, hh = c.lane >> 5;
   for (int m = 0; m < M; ++m) {
     const int pos = pos0 + m, n = pos + 1;
-    for (int d = c.lane; d < HD; d += 64) c.L.qs[h][d] = c.L.qkv[m][h * HD + d] * scale;
+    for (int d = c.lane; d < HD; d += 64) c.L.qs[h][d] = c.L.qkv[m][h * HD + d] * attn32::SCALE;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    float part = 0.f;
-    {
-      const float4* k4 = reinterpret_cast<const float4*>(c.L.Ks[g][kj] + hh * (HD / 2));
-      const float4* q4 = reinterpret_cast<const float4*>(c.L.qs[h] + hh * (HD / 2));
-      float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
-#pragma unroll
-      for (int d4 = 0; d4 < HD / 8; ++d4) {
-        const float4 a = k4[d4], q = q4[d4];
-        d0 = fmaf(q.x, a.x, d0);
-        d1 = fmaf(q.y, a.y, d1);
-        d2 = fmaf(q.z, a.z, d2);
-        d3 = fmaf(q.w, a.w, d3);
-      }
-      part = (d0 + d1) + (d2 + d3);
-    }
-    const float other = __shfl_xor(part, 32, 64);
-    float s = hh == 0 ? part + other : other + part;
-    if (kj >= n) s = -INFINITY;
-    const float mx = wave_max(s);
-    const float pj = kj < n ? expf(s - mx) : 0.f;
-    const float l_run = wave_sum(hh == 0 ? pj : 0.f);
-    const int pji = __float_as_int(pj);
-    // lane = (key half kv = lane >> 5: keys 16 kv + u, dims 4 (lane & 31) .. +3): one 16-B V read per
-    // key, the halves' sums added (keys 0-15 first) by one exchange
-    const int kv = c.lane >> 5, dq = c.lane & 31;
-    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float s = attn32::score(reinterpret_cast<const float4*>(c.L.Ks[g][kj] + hh * (HD / 2)),
+                                  reinterpret_cast<const float4*>(c.L.qs[h] + hh * (HD / 2)), hh);
+    const attn32::Probs pr = attn32::softmax(s, kj, hh, n);
+    const int kv = c.lane >> 5, dq = c.lane & 31;  // kept inside the row loop: hoisting costs 2 VGPRs
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int u0 = 0; u0 < 16; u0 += 8) {
       if (u0 < n) {
         float4 vv[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) vv[u] = *reinterpret_cast<const float4*>(&c.L.Vs[g][16 * kv + u0 + u][4 * dq]);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const float pa = __int_as_float(__builtin_amdgcn_readlane(pji, u0 + u));
-          const float pb = __int_as_float(__builtin_amdgcn_readlane(pji, 16 + u0 + u));
-          const float p = kv ? pb : pa;
-          if (16 * kv + u0 + u < n) {
-            o.x = fmaf(p, vv[u].x, o.x);
-            o.y = fmaf(p, vv[u].y, o.y);
-            o.z = fmaf(p, vv[u].z, o.z);
-            o.w = fmaf(p, vv[u].w, o.w);
-          }
-        }
+        attn32::pv(acc, pr.pji, vv, u0, kv, n);
       }
     }
-    float4 t;
-    t.x = __shfl_xor(o.x, 32, 64);
-    t.y = __shfl_xor(o.y, 32, 64);
-    t.z = __shfl_xor(o.z, 32, 64);
-    t.w = __shfl_xor(o.w, 32, 64);
+    const float4 ov = attn32::finish(acc, pr.l_run);
     if constexpr (Q4) {
       // int4 o_proj input: the padded layout (q4p) and its half-group sums -- lanes dq = 8j .. 8j + 7 of
       // the kv == 0 half hold half group 4h + j
-      const float inv = 1.f / l_run;
-      const float4 ov = make_float4((o.x + t.x) * inv, (o.y + t.y) * inv, (o.z + t.z) * inv, (o.w + t.w) * inv);
       if (kv == 0) *reinterpret_cast<float4*>(&c.L.aq[m][0][0] + q4p(h * HD + 4 * dq)) = ov;
-      float hs = (ov.x + ov.y) + (ov.z + ov.w);
-      hs += __shfl_xor(hs, 1, 64);
-      hs += __shfl_xor(hs, 2, 64);
-      hs += __shfl_xor(hs, 4, 64);
+      const float hs = attn32::half_group_sum(ov);
       if (kv == 0 && (dq & 7) == 0) c.L.ah[m][4 * h + (dq >> 3)] = hs;
     } else if (kv == 0) {
-      const float inv = 1.f / l_run;
-      *reinterpret_cast<float4*>(&c.L.att[m][h * HD + 4 * dq]) =
-          make_float4((o.x + t.x) * inv, (o.y + t.y) * inv, (o.z + t.z) * inv, (o.w + t.w) * inv);
+      *reinterpret_cast<float4*>(&c.L.att[m][h * HD + 4 * dq]) = ov;
     }
   }
   // the new K / V rows -> cache, spread over the workgroups (WG w stores element w of each row:
@@ -920,7 +875,7 @@ __device__ __forceinline__ int gather_code(Ctx& c, int V) {
   b = wk[0];
 #pragma unroll
   for (int i = 1; i < NT / 64; ++i) b = wk[i] > b ? wk[i] : b;
-  c.code = min(max(unpack_argmax(b), 0), V - 1);
+  c.code = sampler::clamp_code(unpack_argmax(b), V);
   return c.code;
 }
 

@@ -44,7 +44,9 @@
 // acc += scale * sum_k q a + bias * sum_k a (the producers publish the half-group sums of the split
 // rows, xs.h); RMSNorm folded as the streaming path's (x * norm weight split, row scale
 // rsqrt(sum x^2 / D + eps) after the dot product); softmax with max subtraction in fp32.
+#include "attn32.h"
 #include "csm_kernels.h"
+#include "gemm_parts.h"
 #include "handoff.h"
 #include "sampler.h"
 #include "xs.h"
@@ -351,9 +353,9 @@ __device__ __forceinline__ void role_q(Ctx& c, int l, int T, const WTile<Q4>& W)
     float a = c.L.ct[t][0][ml][cc] * r, b = c.L.ct[t][0][ml][cc + 1] * r;
     if (n < (HQ + HKV) * HD) {
       const float2 cs = reinterpret_cast<const float2*>(p.rope)[(size_t)p.step * (HD / 2) + (n % HD) / 2];
-      const float y0 = a * cs.x - b * cs.y, y1 = b * cs.x + a * cs.y;
-      a = y0;
-      b = y1;
+      const float2 y = rope_rotate(a, b, cs);
+      a = y.x;
+      b = y.y;
     }
     if (m < p.M) {
       __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, make_float2(a, b)), rsrc(p.qkv), (int)(((size_t)m * QKV + n) * 4), 0, SC1);
@@ -444,12 +446,10 @@ __device__ __forceinline__ void role_a(Ctx& c, int l) {
   const int lane = c.lane;
   c.sub(7);
   if (m < p.M) {
-    const float scale = 0.08838834764831845f;  // 1 / sqrt(128)
     float2 qv, kv2, vv2;
     if (l == 0) {
       // the row's code: arg-max of the previous head's partials (or the sampler's single partial)
-      const unsigned long long best = wave_argmax_partials(p.part + (size_t)m * p.part_stride, p.part_n, lane);
-      const int code = min(max(unpack_argmax(best), 0), p.V - 1);
+      const int code = gp::argmax_code(p.part + (size_t)m * p.part_stride, p.part_n, lane, p.V);
       const float* trow = p.qkv0_tab + (size_t)code * QKV;  // RoPE'd q | k | v of layer 0 (static table)
       qv = reinterpret_cast<const float2*>(trow + h * HD)[lane];
       kv2 = reinterpret_cast<const float2*>(trow + HQ * HD + g * HD)[lane];
@@ -490,9 +490,8 @@ __device__ __forceinline__ void role_a(Ctx& c, int l) {
         const float rs = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc(p.qkvp + (size_t)2 * RMAX * QKV),
                                                                                        (4 * h * RMAX + m) * 4, 0, SC1));
         const float2 cs = reinterpret_cast<const float2*>(p.rope)[(size_t)pos * (HD / 2) + lane];
-        auto rot = [&](float a, float b) { return make_float2(a * cs.x - b * cs.y, b * cs.x + a * cs.y); };
-        qv = rot((q0.x + q1.x) * rs, (q0.y + q1.y) * rs);
-        kv2 = rot((k0.x + k1.x) * rs, (k0.y + k1.y) * rs);
+        qv = rope_rotate((q0.x + q1.x) * rs, (q0.y + q1.y) * rs, cs);
+        kv2 = rope_rotate((k0.x + k1.x) * rs, (k0.y + k1.y) * rs, cs);
         vv2 = make_float2((v0.x + v1.x) * rs, (v0.y + v1.y) * rs);
         if (h % (HQ / HKV) == 0) {  // KVCache.update_and_fetch: this kv head's row at pos
           const size_t o = (((size_t)m * HKV + g) * p.S_cap + pos) * HD + 2 * lane;
@@ -506,7 +505,7 @@ __device__ __forceinline__ void role_a(Ctx& c, int l) {
         vv2 = ld8(row, ((HQ + HKV) * HD + g * HD + 2 * lane) * 4);
       }
     }
-    *reinterpret_cast<float2*>(&c.L.at.qsh[h][2 * lane]) = make_float2(qv.x * scale, qv.y * scale);
+    *reinterpret_cast<float2*>(&c.L.at.qsh[h][2 * lane]) = make_float2(qv.x * attn32::SCALE, qv.y * attn32::SCALE);
     *reinterpret_cast<float2*>(&c.L.at.kn[h][2 * lane]) = kv2;
     *reinterpret_cast<float2*>(&c.L.at.vn[h][2 * lane]) = vv2;
     c.sub(9);
@@ -514,32 +513,12 @@ __device__ __forceinline__ void role_a(Ctx& c, int l) {
   __syncthreads();  // stage_kv's rows (every wave) and this wave's own rows
   c.mark(3);
   if (m < p.M) {
-    // lane = (key kj = lane & 31, half hh of the head dims): scores from two half dots added by one
-    // shuffle, max-subtracted softmax, P.V in key order (lane = key half kv, dims 4 dq .. + 3)
+    // scores, softmax, P.V: the arithmetic and lane maps of attn32.h
     const int kj = lane & 31, hh = lane >> 5, kv = lane >> 5, dq = lane & 31;
-    float s;
-    {
-      const float* krow = kj < pos ? &c.L.at.Ks[g][kj][0] : &c.L.at.kn[h][0];
-      const f4* kr = reinterpret_cast<const f4*>(krow + hh * (HD / 2));
-      const f4* qr = reinterpret_cast<const f4*>(&c.L.at.qsh[h][hh * (HD / 2)]);
-      float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
-#pragma unroll
-      for (int d4 = 0; d4 < HD / 8; ++d4) {
-        const f4 a = kr[d4], q4 = qr[d4];
-        d0 = fmaf(q4.x, a.x, d0);
-        d1 = fmaf(q4.y, a.y, d1);
-        d2 = fmaf(q4.z, a.z, d2);
-        d3 = fmaf(q4.w, a.w, d3);
-      }
-      const float part = (d0 + d1) + (d2 + d3);
-      const float other = __shfl_xor(part, 32, 64);
-      s = hh == 0 ? part + other : other + part;
-      if (kj >= n) s = -INFINITY;
-    }
-    const float mx = wave_max(s);
-    const float pj = kj < n ? expf(s - mx) : 0.f;
-    const float l_run = wave_sum(hh == 0 ? pj : 0.f);
-    const int pji = __float_as_int(pj);
+    const float* krow = kj < pos ? &c.L.at.Ks[g][kj][0] : &c.L.at.kn[h][0];
+    const float s = attn32::score(reinterpret_cast<const f4*>(krow + hh * (HD / 2)),
+                                  reinterpret_cast<const f4*>(&c.L.at.qsh[h][hh * (HD / 2)]), hh);
+    const attn32::Probs pr = attn32::softmax(s, kj, hh, n);
     f4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u0 = 0; u0 < 16; u0 += 8) {
@@ -550,27 +529,13 @@ __device__ __forceinline__ void role_a(Ctx& c, int l) {
           const int jj = 16 * kv + u0 + u;
           vv[u] = *reinterpret_cast<const f4*>(jj < pos ? &c.L.at.Vs[g][jj][4 * dq] : &c.L.at.vn[h][4 * dq]);
         }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const float pa = __int_as_float(__builtin_amdgcn_readlane(pji, u0 + u));
-          const float pb = __int_as_float(__builtin_amdgcn_readlane(pji, 16 + u0 + u));
-          const float pw = kv ? pb : pa;
-          if (16 * kv + u0 + u < n) {
-            acc.x = fmaf(pw, vv[u].x, acc.x);
-            acc.y = fmaf(pw, vv[u].y, acc.y);
-            acc.z = fmaf(pw, vv[u].z, acc.z);
-            acc.w = fmaf(pw, vv[u].w, acc.w);
-          }
-        }
+        attn32::pv(acc, pr.pji, vv, u0, kv, n);
       }
     }
-    const float inv = 1.f / l_run;
-    const float t0 = __shfl_xor(acc.x, 32, 64), t1 = __shfl_xor(acc.y, 32, 64), t2 = __shfl_xor(acc.z, 32, 64),
-                t3 = __shfl_xor(acc.w, 32, 64);
-    const f32x4_t o = {(acc.x + t0) * inv, (acc.y + t1) * inv, (acc.z + t2) * inv, (acc.w + t3) * inv};
+    const f4 o = attn32::finish(acc, pr.l_run);
     if (lane < 32) st16(p.xs_att, xs::off(D, m, h * HD + 4 * dq), o);
     if constexpr (Q4) {  // half group (h * 128 + 4 dq) / 32: lanes dq = 8j .. 8j + 7, columns in order
-      const float hs = sum8((o.x + o.y) + (o.z + o.w));
+      const float hs = attn32::half_group_sum(o);
       if (lane < 32 && (dq & 7) == 0) st4(p.hs_att + (size_t)((h * HD + 4 * dq) / 32) * RMAX + m, hs);
     }
   }
