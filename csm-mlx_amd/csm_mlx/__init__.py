@@ -11,6 +11,7 @@ from . import nn
 from .adapters import load_adapters
 from .batching import SlotBatch, StreamChunk, generate_queue, stream_generate_queue
 from .generation import generate, generate_batch, generate_frame, stream_generate
+from .ingest import StreamEncoder
 from .models import CSM, ModelArgs, csm_1b
 from .prefix import ContextPrefix, cache_context
 from .sampling import make_logits_processors, make_sampler
@@ -18,7 +19,8 @@ from .segment import Segment
 
 __all__ = ["generate", "stream_generate", "CSM", "csm_1b", "Segment", "generate_frame", "generate_batch",
            "make_sampler", "make_logits_processors", "ModelArgs", "nn", "load_adapters", "SlotBatch", "generate_queue",
-           "StreamChunk", "stream_generate_queue", "ContextPrefix", "cache_context"]
+           "StreamChunk", "stream_generate_queue", "ContextPrefix", "cache_context",
+           "StreamEncoder"]
 
 _OUT_OF_SCOPE = {"CSMDataset", "CSMTrainer", "TrainArgs"}
 

@@ -44,6 +44,7 @@ class MimiCodec:
         t = mimi_rope_table(m, n_pos)
         _lib.check(L.mimi_set_rope_table(h, _lib.ptr(t), t.shape[0], t.shape[1] * 2))
         self._stream = None    # the streaming state: None, the batch size of a decode_step stream, or _SLOTS
+        self._enc_stream = None    # the batch size of the encode_step streams (rows 0..B-1 of the encode slots)
 
     def __del__(self):
         try:
@@ -160,6 +161,7 @@ class MimiCodec:
     def reset_state(self, batch_size: int = 1):
         _lib.check(_lib.lib().mimi_reset_state(self._h, batch_size))
         self._stream = batch_size
+        self._enc_stream = None    # encode_step's streams start again too (moshi: one reset for both halves)
 
     def decode_step(self, codes: np.ndarray) -> np.ndarray:
         """One frame: (B, n_q, 1) or (B, n_q) -> (B, 1, frame_size)."""
@@ -204,3 +206,41 @@ class MimiCodec:
         _lib.check(_lib.lib().mimi_decode_slots(self._h, B, int(n), src, 1 if on_device else 0, int(F_cap),
                                                 int(first_row), _lib.ptr(act), _lib.ptr(pcm)))
         return pcm
+
+    # ------------------------------------------------------------------ streaming encode
+    def encode_slot_reset(self, b: int):
+        """Row b of the streaming encoder starts a new stream (mimi_encode_slot_reset; enqueued, not waited
+        for).  The encoder's slots are independent of the decoder's streaming state."""
+        _lib.check(_lib.lib().mimi_encode_slot_reset(self._h, int(b)))
+
+    def encode_slots(self, pcm: np.ndarray, active=None) -> np.ndarray:
+        """n whole frames of every slot in one pass (mimi_encode_slots): (B, n * frame_size) or
+        (B, 1, n * frame_size) float32 -> (B, n_q, n) int32, row b continuing slot b's stream.  ``active``
+        (B,), default all: an inactive slot's row is not codes, and its stream stays where it was."""
+        x = np.asarray(pcm, np.float32)
+        if x.ndim == 3:
+            x = x[:, 0, :]
+        if x.ndim != 2:
+            raise ValueError(f"expected pcm (B, n * {self.m.frame_size}), got {x.shape}")
+        B, N = x.shape
+        if N % self.m.frame_size:
+            raise ValueError(f"encode_slots takes whole frames: {N} samples is no multiple of {self.m.frame_size}")
+        n = N // self.m.frame_size
+        act = np.ones(B, np.uint8) if active is None else np.ascontiguousarray(np.asarray(active).astype(bool), np.uint8)
+        if act.shape != (B,):
+            raise ValueError(f"expected an active mask ({B},), got {act.shape}")
+        x = np.ascontiguousarray(x)
+        codes = np.zeros((B, self.m.n_q, n), np.int32)
+        _lib.check(_lib.lib().mimi_encode_slots(self._h, B, n, _lib.ptr(x), _lib.ptr(act), _lib.ptr(codes)))
+        return codes
+
+    def encode_step(self, pcm: np.ndarray) -> np.ndarray:
+        """moshi ``Mimi.encode_step``: (B, 1, n * frame_size) or (B, n * frame_size) -> (B, n_q, n), rows
+        0..B-1 continuing their streams.  A change of B, or ``reset_state``, starts them again."""
+        x = np.asarray(pcm, np.float32)
+        B = x.shape[0]
+        if self._enc_stream != B:
+            for b in range(B):
+                self.encode_slot_reset(b)
+            self._enc_stream = B
+        return self.encode_slots(x)

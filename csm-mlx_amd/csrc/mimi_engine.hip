@@ -100,6 +100,18 @@ struct mimi_codec {
   bool slot_mode = false;
   int* slot_pos = nullptr;  // [B_max]
   std::vector<int> slot_pos_host;
+  // streaming encoder (mimi_encode_slot_reset / mimi_encode_slots), allocated by the first reset: every row a
+  // slot with its own encode stream, whatever the decoder's streaming mode is
+  bool enc_ready = false;
+  std::vector<float*> enc_hist;   // per encoder op input history [B_max][cin][op_pad]
+  float* enc_down_hist = nullptr;  // the downsample conv's [B_max][D][s]
+  // encoder-transformer KV of the streams (not ekc / evc, which every one-shot encode overwrites), with one
+  // spare row B_max: where an inactive slot's keys go when they would not fit behind its position
+  std::vector<float*> enc_kc, enc_vc;
+  int* enc_pos = nullptr;  // [B_max] latent position (device; the host mirror serves the capacity check only)
+  std::vector<int> enc_pos_host;
+  int* enc_rowtab = nullptr;  // the spare-row pass's per-row {slot, position} tables, 2 x [rows]
+  size_t enc_rowtab_n = 0;
 
   void* alloc(size_t bytes) {
     void* p = nullptr;
@@ -115,6 +127,7 @@ struct mimi_codec {
     if (dcodes) (void)hipFree(dcodes);
     if (rvq_r) (void)hipFree(rvq_r);
     if (rvq_p) (void)hipFree(rvq_p);
+    if (enc_rowtab) (void)hipFree(enc_rowtab);
     if (st) (void)hipStreamDestroy(st);
   }
   int op_cin(const MOp& o) const {
@@ -333,13 +346,17 @@ LinParams lin_params(mimi_codec* m, const float* x, int M, int K, const float* W
 
 // x rows [M = B*T][D] in place through the codec transformer; positions offset..offset+T-1, or with slot_pos
 // (device, [B]) utterance b's at slot_pos[b]..slot_pos[b]+T-1: the T rows are then T / downsample_stride frames
-// of one call, and in the moshi_mlx mode each sees the keys a decode_step call of its own would (ATTN_FRAMES)
+// of one call, and in the moshi_mlx mode each sees the keys a decode_step call of its own would (ATTN_FRAMES).
+// row_b / row_pos (device, [M]): every row's cache row and position from these tables instead.
 void run_transformer(mimi_codec* m, std::vector<MTLayer>& T, std::vector<float*>& kc, std::vector<float*>& vc, int B,
-                     int Tn, int offset, const int* slot_pos = nullptr) {
+                     int Tn, int offset, const int* slot_pos = nullptr, const int* row_b = nullptr,
+                     const int* row_pos = nullptr) {
   const mimi_dims& d = m->d;
   const int D = d.dimension, M = B * Tn, H = d.num_heads, hd = m->hd, F = d.dim_feedforward;
   hipStream_t st = m->st;
   RowMap rm{Tn, 0, slot_pos, offset};
+  rm.row_b = row_b;
+  rm.row_pos = row_pos;
   for (size_t l = 0; l < T.size(); ++l) {
     MTLayer& L = T[l];
     launch_layernorm_rows(m->R, D, L.n1w, L.n1b, d.norm_eps, m->Rh, M, st);
@@ -487,6 +504,70 @@ Pcm decoder_pcm(const mimi_codec* m, int n_lat) {
   for (const MOp& o : m->dec_ops)
     if (o.kind == 1) n *= m->convtrs[o.idx].s;
   return Pcm{m->dec_ops.size() % 2 == 0 ? m->W0 : m->W1, n};
+}
+
+// The streaming encoder SEANet: n new samples per slot (whole frames, so every strided conv divides its input)
+// behind conv0's history in m->W0, every op on its window [history | new] as run_decoder_seanet runs the
+// decoder's, the histories rolled by one launch per op for the active slots only.  Returns the buffer holding
+// the dense output [B][dimension][*n_out].
+float* run_encoder_stream(mimi_codec* m, int B, int n, const MimiSlotMask& active, int* n_out_lat) {
+  const auto& ops = m->enc_ops;
+  float* bufs[2] = {m->W0, m->W1};
+  int cur = 0;
+  bool in_elu = false;
+  for (size_t i = 0; i < ops.size(); ++i) {
+    const MOp& o = ops[i];
+    const int P = m->op_pad(o), cin = m->op_cin(o), cs_in = P + n;
+    float* in = bufs[cur];
+    launch_mimi_window_roll(m->enc_hist[i], in, B, cin, P, n, active, nullptr, m->st);
+    const int n_out = o.kind == 0 ? n / m->convs[o.idx].stride : n;
+    const bool last = i + 1 == ops.size();
+    const int P_next = last ? 0 : m->op_pad(ops[i + 1]);
+    // as in the decoder: an output that only an ELU-input conv reads is stored as ELU(y), and so is its history
+    const bool out_elu = mimi_elu_pre() && !last && ops[i + 1].kind == 0 && m->convs[ops[i + 1].idx].elu;
+    run_window_op(m, o, Act{in, cs_in, 0, cs_in}, P, Act{bufs[cur ^ 1], P_next + n_out, P_next, n_out}, B, in_elu,
+                  out_elu);
+    in_elu = out_elu;
+    n = n_out;
+    cur ^= 1;
+  }
+  *n_out_lat = n;
+  return bufs[cur];
+}
+
+size_t encoder_stream_ws(mimi_codec* m, int n) {  // max window elements per slot
+  size_t best = 0;
+  for (size_t i = 0; i < m->enc_ops.size(); ++i) {
+    const MOp& o = m->enc_ops[i];
+    best = std::max(best, (size_t)m->op_cin(o) * (m->op_pad(o) + n));
+    if (o.kind == 0) n /= m->convs[o.idx].stride;
+    best = std::max(best, (size_t)m->op_cout(o) * (n + 8));
+  }
+  return std::max(best, (size_t)m->d.dimension * (m->d.downsample_stride + n + 8));
+}
+
+int mimi_frame_size(const mimi_codec* m) {
+  int fs = m->d.downsample_stride;
+  for (int r = 0; r < m->d.n_ratios; ++r) fs *= m->d.ratios[r];
+  return fs;
+}
+
+// Slot b's encoder histories zeroed and its position set to 0 (b < 0: every slot's): one launch, no wait
+void enc_slot_reset_launch(mimi_codec* m, int b) {
+  MimiSlotResetParams p{};
+  for (size_t i = 0; i < m->enc_hist.size(); ++i) {
+    if (!m->enc_hist[i]) continue;
+    if (p.n >= MIMI_SLOT_BUFS - 1) throw CsmError(CSM_ERR_ARG, "codec with more streaming buffers than the slot reset table");
+    p.buf[p.n] = m->enc_hist[i];
+    p.per[p.n++] = m->op_cin(m->enc_ops[i]) * m->op_pad(m->enc_ops[i]);
+  }
+  p.buf[p.n] = m->enc_down_hist;
+  p.per[p.n++] = m->d.dimension * m->d.downsample_stride;
+  p.slot_pos = m->enc_pos; p.b = b; p.B = m->B_max;
+  launch_mimi_slot_reset(p, m->st);
+  HIPCHK(hipGetLastError());
+  if (b < 0) std::fill(m->enc_pos_host.begin(), m->enc_pos_host.end(), 0);
+  else m->enc_pos_host[b] = 0;
 }
 
 }  // namespace
@@ -899,6 +980,117 @@ int mimi_decode_slots(mimi_codec* m, int B, int n, const int32_t* hist, int code
     const Pcm out = decoder_pcm(m, steps);
     HIPCHK(hipMemcpyAsync(pcm, out.p, (size_t)B * out.n * 4, hipMemcpyDeviceToHost, m->st));
     HIPCHK(hipStreamSynchronize(m->st));
+    HIPCHK(hipGetLastError());
+  }
+  CSM_CATCH
+}
+
+int mimi_encode_slot_reset(mimi_codec* m, int b) {
+  CSM_TRY {
+    if (!m) throw CsmError(CSM_ERR_ARG, "null codec");
+    if (b < 0 || b >= m->B_max) throw CsmError(CSM_ERR_ARG, "codec slot index out of range");
+    if (m->B_max > MIMI_SLOTS_MAX) throw CsmError(CSM_ERR_ARG, "a streaming encoder serves at most 256 slots");
+    HIPCHK(hipSetDevice(m->dev));
+    if (!m->enc_ready) {  // the first reset allocates the state (zeroed: every row an idle slot at position 0)
+      const mimi_dims& d = m->d;
+      for (const MOp& o : m->enc_ops) {
+        const int P = m->op_pad(o);
+        m->enc_hist.push_back(P > 0 ? (float*)m->alloc((size_t)m->B_max * m->op_cin(o) * P * 4) : nullptr);
+      }
+      m->enc_down_hist = (float*)m->alloc((size_t)m->B_max * d.dimension * d.downsample_stride * 4);
+      const size_t kv = (size_t)(m->B_max + 1) * d.num_heads * m->S_cap * m->hd * 4;
+      for (int l = 0; l < d.num_layers; ++l) {
+        m->enc_kc.push_back((float*)m->alloc(kv));
+        m->enc_vc.push_back((float*)m->alloc(kv));
+      }
+      m->enc_pos = (int*)m->alloc((size_t)m->B_max * 4);
+      m->enc_pos_host.assign(m->B_max, 0);
+      m->enc_ready = true;
+    }
+    enc_slot_reset_launch(m, b);
+  }
+  CSM_CATCH
+}
+
+int mimi_encode_slots(mimi_codec* m, int B, int n, const float* pcm, const uint8_t* active, int32_t* codes) {
+  CSM_TRY {
+    if (!m || !pcm || !active || !codes) throw CsmError(CSM_ERR_ARG, "null codec, pcm, active mask or codes");
+    if (!m->enc_ready) throw CsmError(CSM_ERR_STATE, "mimi_encode_slot_reset must precede mimi_encode_slots");
+    if (B <= 0 || B > m->B_max || B > MIMI_SLOTS_MAX) throw CsmError(CSM_ERR_ARG, "bad slot count");
+    if (n < 1) throw CsmError(CSM_ERR_ARG, "bad frame count");
+    const mimi_dims& d = m->d;
+    const int s = d.downsample_stride, D = d.dimension, cd = d.codebook_dim;
+    if ((int64_t)n * s + 4 > m->S_cap) throw CsmError(CSM_ERR_ARG, "more frames than the codec capacity");
+    const int steps = n * s, N = n * mimi_frame_size(m);
+    // refused before anything is launched: no stream changes
+    for (int b = 0; b < B; ++b)
+      if (active[b] && m->enc_pos_host[b] + steps + 4 > m->S_cap)
+        throw CsmError(CSM_ERR_ARG, "slot " + std::to_string(b) + ": stream longer than the codec capacity");
+    HIPCHK(hipSetDevice(m->dev));
+    hipStream_t st = m->st;
+    ensure_ws(m, encoder_stream_ws(m, N) * B + 64, (size_t)B * steps + 8);
+    MimiSlotMask mask{};
+    bool spare = false;  // an inactive slot too near the end of its cache for this pass's keys
+    for (int b = 0; b < B; ++b) {
+      mask.v[b] = active[b] ? 1 : 0;
+      spare = spare || (!active[b] && m->enc_pos_host[b] + steps + 4 > m->S_cap);
+    }
+    // pcm rows behind conv0's history
+    const int P0 = m->op_pad(m->enc_ops[0]);
+    HIPCHK(hipMemcpy2DAsync(m->W0 + P0, (size_t)(P0 + N) * 4, pcm, (size_t)N * 4, (size_t)N * 4, (size_t)B,
+                            hipMemcpyHostToDevice, st));
+    int n25 = 0;
+    float* lat = run_encoder_stream(m, B, N, mask, &n25);
+    if (n25 != steps) throw CsmError(CSM_ERR_HIP, "mimi streaming encoder: frame bookkeeping");
+    launch_conv_to_rows(lat, B, D, steps, D * steps, steps, 0, m->R, st);
+    // an inactive slot's rows run at its own position, on keys it overwrites when it goes on; one that has no
+    // room left there runs in the caches' spare row from position 0 (per-row tables from the host mirror)
+    std::vector<int> tab;
+    if (spare) {
+      const size_t M = (size_t)B * steps;
+      tab.resize(2 * M);
+      for (int b = 0; b < B; ++b) {
+        const bool sp = !active[b] && m->enc_pos_host[b] + steps + 4 > m->S_cap;
+        for (int t = 0; t < steps; ++t) {
+          tab[(size_t)b * steps + t] = sp ? m->B_max : b;
+          tab[M + (size_t)b * steps + t] = (sp ? 0 : m->enc_pos_host[b]) + t;
+        }
+      }
+      grow(m->enc_rowtab, m->enc_rowtab_n, 2 * M);
+      HIPCHK(hipMemcpyAsync(m->enc_rowtab, tab.data(), 2 * M * 4, hipMemcpyHostToDevice, st));
+      run_transformer(m, m->etr, m->enc_kc, m->enc_vc, B, steps, 0, m->enc_pos, m->enc_rowtab, m->enc_rowtab + M);
+    } else {
+      run_transformer(m, m->etr, m->enc_kc, m->enc_vc, B, steps, 0, m->enc_pos);
+    }
+    // downsample (k = 2s, stride s) on its window; a stream's first call pads with its first latent step
+    float* win = lat == m->W0 ? m->W1 : m->W0;
+    float* out = lat;
+    launch_rows_to_conv(m->R, B, D, steps, win, D * (s + steps), s + steps, s, st);
+    launch_mimi_window_roll(m->enc_down_hist, win, B, D, s, steps, mask, m->enc_pos, st);
+    const MConv down{D, D, 2 * s, s, 1, 0, m->down_w, nullptr};
+    launch_conv1d(conv_params(m, down, Act{win, s + steps, 0, s + steps}, Act{out, n, 0, n}, B, 0), st);
+    launch_conv_to_rows(out, B, D, n, D * n, n, 0, m->R, st);
+    const int M = B * n;
+    m->r_rows = (size_t)M;  // R: the pre-RVQ latent, read only from here on
+    grow(m->dcodes, m->dcodes_n, (size_t)B * d.n_q * n);
+    for (int q = 0; q < 2; ++q) {
+      launch_linear(lin_params(m, m->R, M, D, m->rvq_in[q], cd, m->Rh), st);
+      const int k0 = q == 0 ? 0 : 1, k1 = q == 0 ? 1 : d.n_q;
+      if (k1 <= k0) continue;
+      if (M >= 256 && rvq_gemm_eligible(cd, d.bins)) {  // the rule of mimi_encode_rows
+        grow(m->rvq_r, m->rvq_r_n, (size_t)2 * M * cd);
+        grow(m->rvq_p, m->rvq_p_n, 2 * rvq_gemm_parts(M, d.bins));
+        launch_rvq_encode_gemm(m->Rh, M, n, cd, m->cb, m->cbT, m->c2half, d.bins, k0, k1, d.n_q, m->dcodes, m->rvq_r,
+                               m->rvq_p, st);
+      } else {
+        launch_rvq_encode(m->Rh, M, n, cd, m->cb, m->c2half, d.bins, k0, k1, d.n_q, m->dcodes, st);
+      }
+    }
+    for (int b = 0; b < B; ++b)
+      if (active[b]) m->enc_pos_host[b] += steps;
+    launch_mimi_slot_advance(m->enc_pos, mask, B, steps, st);
+    HIPCHK(hipMemcpyAsync(codes, m->dcodes, (size_t)B * d.n_q * n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
   }
   CSM_CATCH

@@ -132,6 +132,12 @@ struct MimiSlotMask {
 void launch_mimi_slot_reset(const MimiSlotResetParams& p, hipStream_t st);
 // slot_pos[b] += steps where active.v[b], b < B
 void launch_mimi_slot_advance(int* slot_pos, const MimiSlotMask& active, int B, int steps, hipStream_t st);
+// The streaming encoder's window roll (mimi_encode_slots), once per op: rows (slot b < B, channel c < C) of the
+// window win [B][C][P + n_new] get their head from hist [B_max][C][P]; an active slot's history then becomes
+// the window's last P samples (right for n_new < P).  edge_pos (device, [B]; else null): a slot at position
+// 0 gets the head filled with its first new sample (replicate pad).  B <= MIMI_SLOTS_MAX.
+void launch_mimi_window_roll(float* hist, float* win, int B, int C, int P, int n_new, const MimiSlotMask& active,
+                             const int* edge_pos, hipStream_t st);
 
 // Kernel launches the codec has made in this process (a host counter, for the launch accounting of the benches)
 long long mimi_kernel_launches();

@@ -905,3 +905,34 @@ __global__ void mimi_slot_advance_kernel(int* slot_pos, MimiSlotMask active, int
 void launch_mimi_slot_advance(int* slot_pos, const MimiSlotMask& active, int B, int steps, hipStream_t st) {
   MIMI_LAUNCH(mimi_slot_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, slot_pos, active, B, steps);
 }
+
+// ============================================================================ streaming encoder windows
+// One launch per encoder op of a mimi_encode_slots pass, a thread per (slot, channel) row of the op's input
+// window [P history | n_new new] (rows dense, P + n_new floats apart; the histories [slot][channel][P]):
+// the head is written from the slot's history, then, where the slot is active, the history becomes the last
+// P samples of the whole window (read back from the window, so n_new < P keeps the history's own tail).
+// edge_pos (the downsample conv): a slot at position 0 gets its first new sample in the head, the replicate
+// left pad of a one-shot encode; the other ops' constant pad is the zero history a reset leaves.
+__global__ __launch_bounds__(256) void mimi_window_roll_kernel(float* hist, float* win, int C, int P, int n_new,
+                                                               int rows, MimiSlotMask active, const int* edge_pos) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  const int b = r / C;
+  float* h = hist + (size_t)r * P;
+  float* w = win + (size_t)r * (P + n_new);
+  if (edge_pos && edge_pos[b] == 0) {
+    const float v = w[P];
+    for (int i = 0; i < P; ++i) w[i] = v;
+  } else {
+    for (int i = 0; i < P; ++i) w[i] = h[i];
+  }
+  if (active.v[b])
+    for (int i = 0; i < P; ++i) h[i] = w[n_new + i];
+}
+void launch_mimi_window_roll(float* hist, float* win, int B, int C, int P, int n_new, const MimiSlotMask& active,
+                             const int* edge_pos, hipStream_t st) {
+  if (P <= 0 || n_new <= 0 || B <= 0) return;
+  const int rows = B * C;
+  MIMI_LAUNCH(mimi_window_roll_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, hist, win, C, P, n_new, rows,
+              active, edge_pos);
+}

@@ -291,6 +291,34 @@ int mimi_decode_step(mimi_codec* m, int B, const int32_t* codes, float* pcm);
 int mimi_slot_reset(mimi_codec* m, int b);
 int mimi_decode_slots(mimi_codec* m, int B, int n, const int32_t* hist, int codes_on_device, int F_cap,
                       int first_row, const uint8_t* active, float* pcm);
+/* Streaming encode, the other half of the moshi Mimi streaming interface: every row of the codec is a slot with
+ * an encode stream of its own (conv histories, encoder-transformer KV, latent position), so audio arriving in
+ * blocks is encoded in one pass per tick for all callers.  The state is allocated by the first
+ * mimi_encode_slot_reset, is separate from the decoder's streaming state and from the one-shot encode's KV:
+ * mimi_reset_state, mimi_decode, mimi_decode_slots, mimi_decode_step, mimi_encode and mimi_encode_rows neither
+ * read nor change it, and these two calls leave the decoder's slot mode alone.
+ *   mimi_encode_slot_reset  row b starts a new stream: its histories zeroed and its position set to 0 by one
+ *                      small launch on the codec stream (enqueued, not waited for).  The first call allocates
+ *                      the state, every row an idle slot at position 0.
+ *                      CSM_ERR_ARG: b outside [0, max_batch), or a codec of more than 256 rows.
+ *   mimi_encode_slots  n whole frames of rows 0..B-1 in one pass: pcm [B][n * frame_size] float32 host ->
+ *                      codes [B][n_q][n] int32 host; waits for the codec stream.  A slot's codes equal the
+ *                      frame-by-frame encode of its stream alone however the frames are split over calls: in
+ *                      the causal attention mode the one-shot encode of the same audio, in the moshi_mlx mode
+ *                      each frame sees its own frame's keys and the past (a call per frame).  No end-of-clip
+ *                      padding exists in a stream: a trailing partial frame cannot be encoded.  active[B]
+ *                      (host): an inactive row flows through the pass (its codes mean nothing), but neither its
+ *                      histories nor its position change and its keys land where its next active call
+ *                      overwrites them, so its stream goes on at its next active call without a reset.
+ *                      Afterwards mimi_debug_read "rows" holds the pre-RVQ latent [B * n][dimension], row
+ *                      b * n + f.
+ *                      CSM_ERR_STATE: no mimi_encode_slot_reset yet.  CSM_ERR_ARG: a null pointer, B outside
+ *                      [1, max_batch], n < 1, a codec of more than 256 rows, or an active slot whose position
+ *                      + n * downsample_stride + 4 exceeds the codec's latent capacity (as n *
+ *                      downsample_stride + 4 alone does for any slot): refused before anything is launched,
+ *                      no stream changes. */
+int mimi_encode_slot_reset(mimi_codec* m, int b);
+int mimi_encode_slots(mimi_codec* m, int B, int n, const float* pcm, const uint8_t* active, int32_t* codes);
 
 #ifdef __cplusplus
 }
