@@ -139,6 +139,7 @@ def lib():
             "mimi_encode_slot_reset": ([P, I], I),
             "mimi_encode_slots": ([P, I, I, P, P, P], I),
             "mimi_debug_read": ([P, ctypes.c_char_p, P, I64, ctypes.POINTER(I64)], I),
+            "mimi_kv_read": ([P, I, I, I, I, I, P, P], I),
             "mimi_lab_plan": ([I, P, I, P], I),
             "mimi_lab_conv1d": ([P, I, P, I64, P, I64, P, P, I64, P, P, I64], I),
             "mimi_lab_convtr": ([P, I, P, I64, P, I64, P, P, I64], I),

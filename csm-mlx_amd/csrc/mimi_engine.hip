@@ -573,6 +573,16 @@ void enc_slot_reset_launch(mimi_codec* m, int b) {
 }  // namespace
 
 // =============================================================================== C ABI
+bool mimi_kv_view(mimi_codec* m, int side, int layer, MimiKvView* out) {
+  if (!m || !out || layer < 0 || layer >= m->d.num_layers || (side != 0 && side != 1)) return false;
+  if (side == 1 && !m->enc_ready) return false;
+  const std::vector<float*>& kc = side ? m->enc_kc : m->dkc;
+  const std::vector<float*>& vc = side ? m->enc_vc : m->dvc;
+  if ((size_t)layer >= kc.size() || (size_t)layer >= vc.size()) return false;
+  *out = MimiKvView{kc[layer], vc[layer], m->B_max + side, m->d.num_heads, m->S_cap, m->hd, m->dev, m->st};
+  return true;
+}
+
 extern "C" {
 
 int mimi_create(const mimi_dims* dims, int device, int max_batch, int max_frames, mimi_codec** out) {

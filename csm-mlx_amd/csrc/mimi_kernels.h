@@ -139,6 +139,17 @@ void launch_mimi_slot_advance(int* slot_pos, const MimiSlotMask& active, int B, 
 void launch_mimi_window_roll(float* hist, float* win, int B, int C, int P, int n_new, const MimiSlotMask& active,
                              const int* edge_pos, hipStream_t st);
 
+// A codec's transformer KV caches as the lab door's mimi_kv_read reads them (mimi_engine.hip owns the codec
+// struct): side 0 the decoder's (one-shot, decode_step and slot streams), 1 the streaming encoder's.  k / v
+// [rows][heads][S_cap][hd]; false when the side has no cache yet or the layer is out of range.
+struct mimi_codec;
+struct MimiKvView {
+  const float *k, *v;
+  int rows, heads, S_cap, hd, dev;
+  hipStream_t st;
+};
+bool mimi_kv_view(mimi_codec* m, int side, int layer, MimiKvView* out);
+
 // Kernel launches the codec has made in this process (a host counter, for the launch accounting of the benches)
 long long mimi_kernel_launches();
 void mimi_count_launch();

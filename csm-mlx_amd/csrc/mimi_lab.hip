@@ -1,5 +1,6 @@
 // Mimi codec, lab door: one codec kernel launch on caller-supplied host arrays, and the launchers' own
-// plan for a geometry (include/csm_hip_prof.h).  No codec handle: every entry allocates on the current
+// plan for a geometry (include/csm_hip_prof.h).  No codec handle (but mimi_kv_read, the inspection door of a
+// codec's KV caches, at the end): every entry allocates on the current
 // device, uploads, launches on a stream of its own with its own split-K scratch, downloads and frees.
 // Output buffers arrive with the caller's initial content (a sentinel, or the values an accumulating
 // store adds onto) and are returned whole, so a store outside the addressed region shows.
@@ -260,6 +261,21 @@ int mimi_lab_rvq_encode(int gemm, int M, int T, int cd, int bins, int n_q, int k
     }
     HIPCHK(hipMemcpy(r, dr.p, rn * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(codes, dcodes.p, cn * 4, hipMemcpyDeviceToHost));
+  }
+  CSM_CATCH
+}
+
+int mimi_kv_read(mimi_codec* m, int side, int b, int layer, int first, int rows, float* k, float* v) {
+  CSM_TRY {
+    MimiKvView c{};
+    need(mimi_kv_view(m, side, layer, &c), "kv read: null codec, side (0 decoder, 1 streaming encoder) without a cache, or layer");
+    need(b >= 0 && b < c.rows && first >= 0 && rows >= 1 && (int64_t)first + rows <= c.S_cap, "kv read: row or positions out of range");
+    HIPCHK(hipSetDevice(c.dev));
+    HIPCHK(hipStreamSynchronize(c.st));
+    const size_t run = (size_t)rows * c.hd * 4, pitch = (size_t)c.S_cap * c.hd * 4;
+    const size_t off = ((size_t)b * c.heads * c.S_cap + first) * c.hd;
+    if (k) HIPCHK(hipMemcpy2D(k, run, c.k + off, pitch, run, c.heads, hipMemcpyDeviceToHost));
+    if (v) HIPCHK(hipMemcpy2D(v, run, c.v + off, pitch, run, c.heads, hipMemcpyDeviceToHost));
   }
   CSM_CATCH
 }

@@ -128,6 +128,14 @@ int mimi_lab_rvq_encode(int gemm, int M, int T, int cd, int bins, int n_q, int k
  * "launches" = one int64: the kernel launches the codec code has made in this process so far (a host
  * counter; tools/slots_bench.py --stream divides its growth by the chunks decoded). */
 int mimi_debug_read(mimi_codec* m, const char* what, void* host, int64_t nbytes, int64_t* needed);
+/* Inspection door of a codec's transformer KV caches (as csm_kv_read): positions first .. first+rows-1 of cache
+ * row b in layer `layer`, as k / v [num_heads][rows][head_dim] float32 (either may be NULL).  side 0: the
+ * decoder's cache (rows 0 .. max_batch-1: mimi_decode, mimi_decode_step and the slot streams share it); side 1:
+ * the streaming encoder's (rows 0 .. max_batch-1 the slots, row max_batch its spare row; it exists from the first
+ * mimi_encode_slot_reset on).  Positions run to max_frames * downsample_stride + 15.  Waits for the codec's stream.  CSM_ERR_ARG
+ * for a side, row, layer or position range outside the codec's.  tests/test_mimi_window_gpu.py reads the caches
+ * through it; the product does not call it. */
+int mimi_kv_read(mimi_codec* m, int side, int b, int layer, int first, int rows, float* k, float* v);
 
 #ifdef __cplusplus
 }

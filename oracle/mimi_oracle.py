@@ -146,7 +146,32 @@ class TransformerRef:
     def new_cache(self):
         return [{"k": None, "v": None, "offset": 0} for _ in range(self.m.num_layers)]
 
-    def attn(self, l, x, cache):
+    def keep(self, off, T, S, blk=None):
+        """The (T, S) mask of the keys each of a call's T rows (positions off .. off + T - 1, S = off + T keys
+        cached) attends.  blk: the call is T / blk frames of blk rows, and in the "mlx" mode each frame sees
+        the keys a call of its own would: its own rows and min(context, frame start) past ones (a streaming
+        call of several frames; the causal mode is the same mask with or without it).  The window tests
+        (tests/test_mimi_window_cpu.py) replace this hook with defective ones."""
+        m = self.m
+        qpos = off + np.arange(T)[:, None]
+        kpos = np.arange(S)[None, :]
+        if m.attn_mode == "mlx":
+            if blk is None:
+                return np.broadcast_to(kpos >= S - (T + min(m.context, S - T)), (T, S))
+            f0 = off + np.arange(T)[:, None] // blk * blk                      # the row's frame starts here
+            return (kpos >= f0 - np.minimum(m.context, f0)) & (kpos < f0 + blk)
+        return (kpos <= qpos) & (qpos - kpos < m.context)
+
+    def softmax_av(self, s, keep, Vv):
+        """softmax over the kept keys of scores s (B, H, T, S), times Vv (B, H, S, hd).  A hook as ``keep``."""
+        dt = self.dt
+        s = np.where(keep, s, dt(-np.inf))
+        s = s - s.max(-1, keepdims=True)
+        pr = np.exp(s)
+        pr = pr / pr.sum(-1, keepdims=True)
+        return np.matmul(pr.astype(dt), Vv).astype(dt)
+
+    def attn(self, l, x, cache, blk=None):
         m, w, dt = self.m, self.w, self.dt
         p = f"{self.p}.transformer.layers.{l}.self_attn"
         B, T, d = x.shape
@@ -162,28 +187,18 @@ class TransformerRef:
         cache["k"], cache["v"], cache["offset"] = K, Vv, off + T
         S = K.shape[2]
         s = np.matmul(q, K.transpose(0, 1, 3, 2)).astype(dt) * dt(hd ** -0.5)
-        qpos = off + np.arange(T)[:, None]
-        kpos = np.arange(S)[None, :]
-        if m.attn_mode == "mlx":
-            keep = np.broadcast_to(kpos >= S - (T + min(m.context, S - T)), (T, S))
-        else:
-            keep = (kpos <= qpos) & (qpos - kpos < m.context)
-        s = np.where(keep, s, dt(-np.inf))
-        s = s - s.max(-1, keepdims=True)
-        pr = np.exp(s)
-        pr = pr / pr.sum(-1, keepdims=True)
-        o = np.matmul(pr.astype(dt), Vv).astype(dt).transpose(0, 2, 1, 3).reshape(B, T, d)
+        o = self.softmax_av(s, self.keep(off, T, S, blk), Vv).transpose(0, 2, 1, 3).reshape(B, T, d)
         return np.matmul(o, w[f"{p}.out_proj.weight"].astype(dt, copy=False).T).astype(dt)
 
-    def __call__(self, x_bct, cache):
-        """conv layout in/out (B,C,T)."""
+    def __call__(self, x_bct, cache, blk=None):
+        """conv layout in/out (B,C,T).  blk: ``keep``'s."""
         m, dt = self.m, self.dt
         w = self.w if isinstance(self.w, _Widened) else _Widened(self.w, dt)
         x = x_bct.transpose(0, 2, 1).astype(dt)
         for l in range(m.num_layers):
             p = f"{self.p}.transformer.layers.{l}"
             n1 = layer_norm(x, w[f"{p}.norm1.weight"], w[f"{p}.norm1.bias"], m.norm_eps, dt)
-            x = (x + w[f"{p}.layer_scale_1.scale"] * self.attn(l, n1, cache[l])).astype(dt)
+            x = (x + w[f"{p}.layer_scale_1.scale"] * self.attn(l, n1, cache[l], blk)).astype(dt)
             n2 = layer_norm(x, w[f"{p}.norm2.weight"], w[f"{p}.norm2.bias"], m.norm_eps, dt)
             h = gelu(np.matmul(n2, w[f"{p}.linear1.weight"].T).astype(dt), m.gelu, dt)
             x = (x + w[f"{p}.layer_scale_2.scale"] * np.matmul(h, w[f"{p}.linear2.weight"].T).astype(dt)).astype(dt)
@@ -330,9 +345,12 @@ class OracleMimi:
         self._hist = None
         self._emitted = 0
 
-    def decode_step(self, codes_bk1: np.ndarray, window: int = 0) -> np.ndarray:
+    def decode_step(self, codes_bk1: np.ndarray, window: int = 0, pcm: bool = True) -> np.ndarray:
         """Mimi.decode_step on one frame (B,n_q,1) -> (B,1,frame_size).  Leaves taps["rows"] = the decoder
         transformer's output rows of this frame (B, downsample_stride, D).
+        pcm=False: the stream is stepped without the SEANet (returns None once taps["rows"] is set; such a
+        stream keeps no SEANet history, so every step of it is a pcm=False one): the transformer's 2 rows a
+        step make a float64 stream of hundreds of frames cheap (tests/test_mimi_window_*.py).
 
         The causal convs (upsample, SEANet) are evaluated on the whole history,
         which equals their streaming state machine exactly; the transformer keeps
@@ -341,19 +359,29 @@ class OracleMimi:
         only (its receptive field is < 5 frames, so for window >= 8 the new frame's
         samples are the same values up to BLAS summation order -- checked in
         tests/test_oracle_cpu.py); linear instead of quadratic in the frames."""
-        q = self.quantizer_decode(codes_bk1)
+        return self.decode_steps(codes_bk1, window, pcm)
+
+    def decode_steps(self, codes_bkn: np.ndarray, window: int = 0, pcm: bool = True) -> np.ndarray:
+        """n frames of the decode_step stream in one call, (B,n_q,n) -> (B,1,n*frame_size): what one streaming
+        call of n frames computes (MimiCodec.decode_slots).  The transformer runs the n frames' rows at once,
+        each frame attending what a decode_step call of its own would (TransformerRef.keep's blk; in the causal
+        mode that is the causal window itself).  taps["rows"] = the n frames' rows (B, n*downsample_stride, D).
+        window, pcm: as decode_step (window + n - 1 frames of history serve the n new ones)."""
+        n = codes_bkn.shape[2]
+        q = self.quantizer_decode(codes_bkn)
         self._qhist = q if self._qhist is None else np.concatenate([self._qhist, q], axis=2)
         s = self.m.downsample_stride
-        new = self.upsample(self._qhist[:, :, -2:])[:, :, -s:]   # (depthwise k = 2 s: the last two frames)
-        y = self.dec_tr(new, self._tr_cache)
+        new = self.upsample(self._qhist[:, :, -(n + 1):])[:, :, -n * s:]   # (depthwise k = 2 s: one frame back)
+        self._qhist = self._qhist[:, :, -1:]
+        y = self.dec_tr(new, self._tr_cache, blk=s)
         self.taps = {"rows": y.transpose(0, 2, 1).copy()}
+        if not pcm:
+            return None
         self._hist = y if self._hist is None else np.concatenate([self._hist, y], axis=2)
         fs = self.m.frame_size
         if window > 0:
-            pcm = self._seanet(self.dec_layout, self._hist[:, :, -window * s:])
-            out = pcm[:, :, -fs:]
+            out = self._seanet(self.dec_layout, self._hist[:, :, -(window + n - 1) * s:])[:, :, -n * fs:]
         else:
-            pcm = self._seanet(self.dec_layout, self._hist)
-            out = pcm[:, :, self._emitted: self._emitted + fs]
-        self._emitted += fs
+            out = self._seanet(self.dec_layout, self._hist)[:, :, self._emitted: self._emitted + n * fs]
+        self._emitted += n * fs
         return out

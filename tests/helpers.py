@@ -411,15 +411,18 @@ def f64_reference(args, weights, variant, prompts, codes, block=None):
 MIMI_BAR_MARGIN = BAR_MARGIN
 
 
-def mimi_pair(name, mode, rig=None):
+def mimi_pair(name, mode, rig=None, context=None):
     """(MimiArgs, synthetic weights, float32 oracle, float64 oracle) of a codec config, memoised.
-    rig: a function (m, w) -> new weights applied to the synthetic ones (``mimi_affine_rig``)."""
-    key = ("mimi", name, mode, rig)
+    rig: a function (m, w) -> new weights applied to the synthetic ones (``mimi_affine_rig``);
+    context: the attention window in place of the config's (tests/test_mimi_window_*.py)."""
+    key = ("mimi", name, mode, rig, context)
     if key not in _ORACLES:
         from csm_mlx.config import MIMI_CONFIGURATION
         from csm_mlx.weights import synthetic_mimi_weights
         from oracle.mimi_oracle import OracleMimi
         m = dataclasses.replace(MIMI_CONFIGURATION[name], attn_mode=mode)
+        if context is not None:
+            m = dataclasses.replace(m, context=context)
         w = synthetic_mimi_weights(m)
         if rig is not None:
             w = rig(m, w)

@@ -15,11 +15,15 @@ RVQ_TIE = 1e-5       # oracle RVQ margin below which a code is a tie at float32 
 _REFS = {}
 
 
-def stream_reference(o, pcm, zero_start=False):
+def stream_reference(o, pcm, zero_start=False, whole=False):
     """pcm (N,), N a multiple of the frame size, through oracle ``o`` one frame at a time.
     Returns {"rows": (F, D) pre-RVQ latent, "codes": (n_q, F) int32, "margins": (n_q, F)}.
     zero_start: the downsample conv starts from a zero history instead of the edge sample (the defect a
-    streaming encoder without the stream-start case has; for the CPU facts only)."""
+    streaming encoder without the stream-start case has; for the CPU facts only).
+    whole: the causal SEANet runs once over the whole clip and each frame takes its steps from that (whole
+    frames have no right padding, so these are the values of the per-frame evaluation up to BLAS summation
+    order): linear instead of quadratic in the frames, for the streams of a hundred frames
+    (tests/test_mimi_window_*.py)."""
     m, dt = o.m, o.dt
     fs, s = m.frame_size, m.downsample_stride
     x = np.asarray(pcm, np.float32).reshape(1, 1, -1).astype(dt)
@@ -28,8 +32,9 @@ def stream_reference(o, pcm, zero_start=False):
     cache = o.enc_tr.new_cache()
     dw = o.w["downsample.conv.conv.conv.weight"]
     lat, out = None, []
+    e_all = o._seanet(o.enc_layout, x) if whole else None
     for f in range(F):
-        e = o._seanet(o.enc_layout, x[..., :(f + 1) * fs])[..., -s:]
+        e = o._seanet(o.enc_layout, x[..., :(f + 1) * fs])[..., -s:] if e_all is None else e_all[..., f * s: (f + 1) * s]
         y = o.enc_tr(e, cache)
         lat = y if lat is None else np.concatenate([lat, y], axis=2)
         src = np.concatenate([np.zeros_like(lat[..., :s]), lat], axis=2) if zero_start else lat
@@ -42,12 +47,13 @@ def stream_reference(o, pcm, zero_start=False):
             "margins": np.stack([mg for mg, _ in ms], axis=1)[0]}
 
 
-def stream_pair(o32, o64, pcm, key=None):
+def stream_pair(o32, o64, pcm, key=None, whole=False):
     """{"f32": ..., "f64": ..., "e32": ...} of one stream: both references and the float32 one's error in
-    helpers.mimi_errors' unit on the rows (its maximum over the stream's frames).  key: memoise under it."""
+    helpers.mimi_errors' unit on the rows (its maximum over the stream's frames).  key: memoise under it.
+    whole: ``stream_reference``'s."""
     if key is not None and key in _REFS:
         return _REFS[key]
-    r = {"f32": stream_reference(o32, pcm), "f64": stream_reference(o64, pcm)}
+    r = {"f32": stream_reference(o32, pcm, whole=whole), "f64": stream_reference(o64, pcm, whole=whole)}
     r["e32"] = float(mimi_errors(r["f32"]["rows"][None], r["f64"]["rows"][None]).max())
     if key is not None:
         _REFS[key] = r

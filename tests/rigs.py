@@ -132,14 +132,17 @@ def codes_per_utterance(model, prompts, frames, sampler, seeds=None, logits_proc
 
 
 # ----------------------------------------------------------------------------- the codec beside its oracle
-def mimi_codec(name, mode, max_batch, max_frames, rig=None):
+def mimi_codec(name, mode, max_batch, max_frames, rig=None, context=None):
     """(MimiArgs, MimiCodec with synthetic weights, float32 OracleMimi on the same weights).
-    rig: a function (m, w) -> new weights applied to the synthetic ones (helpers.mimi_affine_rig)."""
+    rig: a function (m, w) -> new weights applied to the synthetic ones (helpers.mimi_affine_rig);
+    context: the attention window in place of the config's (tests/test_mimi_window_gpu.py)."""
     from csm_mlx.config import MIMI_CONFIGURATION
     from csm_mlx.mimi import MimiCodec
     from csm_mlx.weights import synthetic_mimi_weights
     from oracle.mimi_oracle import OracleMimi
     m = dataclasses.replace(MIMI_CONFIGURATION[name], attn_mode=mode)
+    if context is not None:
+        m = dataclasses.replace(m, context=context)
     w = synthetic_mimi_weights(m)
     if rig is not None:
         w = rig(m, w)
